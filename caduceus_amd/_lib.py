@@ -143,12 +143,18 @@ SYMBOLS = {
     "cad_is_device_build": (_i, []),
     "cad_embed_fwd": (_i, [C.POINTER(EmbedArgs), _p]),
     "cad_embed_bwd": (_i, [C.POINTER(EmbedBwdArgs), _p]),
+    "cad_embed_bwd_slotted": (_i, [C.POINTER(EmbedBwdArgs), _p, _p]),
+    "cad_embed_bwd_slots": (_i, [C.POINTER(EmbedBwdArgs)]),
     "cad_add_norm_fwd": (_i, [C.POINTER(AddNormArgs), _p]),
     "cad_add_norm_bwd": (_i, [C.POINTER(AddNormBwdArgs), _p]),
+    "cad_add_norm_bwd_slotted": (_i, [C.POINTER(AddNormBwdArgs), _p, _p, _p]),
+    "cad_add_norm_bwd_slots": (_i, [C.POINTER(AddNormBwdArgs)]),
     "cad_conv1d_fwd": (_i, [C.POINTER(Conv1dArgs), _p]),
     "cad_conv1d_bwd": (_i, [C.POINTER(Conv1dBwdArgs), _p]),
     "cad_conv1d_fwd_multi": (_i, [C.POINTER(Conv1dArgs), _i, _p]),
     "cad_conv1d_bwd_multi": (_i, [C.POINTER(Conv1dBwdArgs), _i, _p]),
+    "cad_conv1d_bwd_multi_slotted": (_i, [C.POINTER(Conv1dBwdArgs), _i, C.POINTER(_p), C.POINTER(_p), _p]),
+    "cad_conv1d_bwd_slots": (_i, [C.POINTER(Conv1dBwdArgs)]),
     "cad_scan_fwd": (_i, [C.POINTER(ScanArgs), _p]),
     "cad_scan_chunk_len": (_i64, []),
     "cad_scan_state_floats": (_i64, [_i, _i64, _i64, _i]),

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_kernel(cad_add_nor
 #define ANB_ROWS_MAX 64
 #define ANB_TARGET_BLOCKS 1024
 template <typename TX, typename TY>
-__global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_kernel(cad_add_norm_bwd_args a, int rows_per_wave) {
+__global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_kernel(cad_add_norm_bwd_args a, int rows_per_wave, float* wslots, float* bslots) {
     __shared__ float red[AN_WAVES][64 * AN_KMAX];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -165,7 +165,11 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_kernel(cad_add_nor
             float t = 0.f;
             for (int w = 0; w < AN_WAVES; ++w) t += red[w][c];
             const int oc = a.swap_flip ? (D - 1 - c) : c;
-            if (t != 0.f) atomicAdd(pass == 0 ? &a.dweight[oc] : &a.dbias[oc], t);
+            float* slot = pass == 0 ? wslots : bslots;
+            if (t != 0.f) {
+                if (slot) slot[(int64_t)blockIdx.x * D + oc] = t;
+                else atomicAdd(pass == 0 ? &a.dweight[oc] : &a.dbias[oc], t);
+            }
         }
         __syncthreads();
     }
@@ -306,7 +310,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_vec_kernel(cad_add
 }
 
 template <typename TX, typename TY, int KMAX>
-__global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add_norm_bwd_args a, int rows_per_wave) {
+__global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add_norm_bwd_args a, int rows_per_wave, float* wslots, float* bslots) {
     __shared__ float red[AN_WAVES][64 * KMAX * 4];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -398,7 +402,11 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add
         for (int c = threadIdx.x; c < D; c += blockDim.x) {
             float t = 0.f;
             for (int w = 0; w < AN_WAVES; ++w) t += red[w][c];
-            if (t != 0.f) atomicAdd(pass == 0 ? &a.dweight[c] : &a.dbias[c], t);
+            float* slot = pass == 0 ? wslots : bslots;
+            if (t != 0.f) {
+                if (slot) slot[(int64_t)blockIdx.x * D + c] = t;
+                else atomicAdd(pass == 0 ? &a.dweight[c] : &a.dbias[c], t);
+            }
         }
         __syncthreads();
     }
@@ -448,15 +456,26 @@ extern "C" int cad_add_norm_fwd(const cad_add_norm_args* a, void* stream) {
     return cad_after_launch();
 }
 
-extern "C" int cad_add_norm_bwd(const cad_add_norm_bwd_args* a, void* stream) {
+static int an_bwd_rows_per_wave(const cad_add_norm_bwd_args* a) {
+    const int64_t nrows = a->rows_per_strand * a->n_strands;
+    int64_t rpw = nrows / ((int64_t)AN_WAVES * ANB_TARGET_BLOCKS);
+    rpw = rpw < ANB_ROWS_MIN ? ANB_ROWS_MIN : (rpw > ANB_ROWS_MAX ? ANB_ROWS_MAX : rpw);
+    return (int)rpw;
+}
+
+extern "C" int cad_add_norm_bwd_slots(const cad_add_norm_bwd_args* a) {  // = the backward's workgroups
+    if (!a || a->rows_per_strand <= 0 || (a->n_strands != 1 && a->n_strands != 2)) return 0;
+    const int64_t per_block = (int64_t)AN_WAVES * an_bwd_rows_per_wave(a);
+    return (int)((a->rows_per_strand * a->n_strands + per_block - 1) / per_block);
+}
+
+static int add_norm_bwd(const cad_add_norm_bwd_args* a, float* wslots, float* bslots, void* stream) {
     CAD_CHECK_ARG(a && a->dy && a->sum_saved && a->rstd && a->weight && a->dx && a->dweight);
     CAD_CHECK_ARG(a->rows_per_strand > 0 && a->D > 0 && (a->n_strands == 1 || a->n_strands == 2));
     if (a->D > 64 * AN_KMAX) return CAD_ERR_UNSUPPORTED;
     CadProfScope prof(5, stream);
     const int64_t nrows = a->rows_per_strand * a->n_strands;
-    int64_t rpw = nrows / ((int64_t)AN_WAVES * ANB_TARGET_BLOCKS);
-    rpw = rpw < ANB_ROWS_MIN ? ANB_ROWS_MIN : (rpw > ANB_ROWS_MAX ? ANB_ROWS_MAX : rpw);
-    const int rows_per_wave = (int)rpw;
+    const int rows_per_wave = an_bwd_rows_per_wave(a);
     const int64_t per_block = (int64_t)AN_WAVES * rows_per_wave;
     dim3 grid((unsigned)((nrows + per_block - 1) / per_block)), block(64 * AN_WAVES);
     const bool vec = (a->D % 4) == 0 && (((uintptr_t)a->dy | (uintptr_t)a->dres_out | (uintptr_t)a->sum_saved |
@@ -464,13 +483,13 @@ extern "C" int cad_add_norm_bwd(const cad_add_norm_bwd_args* a, void* stream) {
 #define AN_BWD(TX, TY)                                                                  \
     do {                                                                                \
         if (vec && a->D <= 256)                                                         \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a, rows_per_wave);  \
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
         else if (vec && a->D <= 512)                                                    \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a, rows_per_wave);  \
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
         else if (vec)                                                                   \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a, rows_per_wave);  \
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
         else                                                                            \
-            CAD_LAUNCH((add_norm_bwd_kernel<TX, TY>), grid, block, 0, stream, *a, rows_per_wave);      \
+            CAD_LAUNCH((add_norm_bwd_kernel<TX, TY>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);      \
     } while (0)
     if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F32)
         AN_BWD(float, float);
@@ -481,4 +500,16 @@ extern "C" int cad_add_norm_bwd(const cad_add_norm_bwd_args* a, void* stream) {
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
+}
+
+extern "C" int cad_add_norm_bwd(const cad_add_norm_bwd_args* a, void* stream) { return add_norm_bwd(a, nullptr, nullptr, stream); }
+
+extern "C" int cad_add_norm_bwd_slotted(const cad_add_norm_bwd_args* a, float* wslots, float* bslots, void* stream) {
+    CAD_CHECK_ARG(a && wslots && (!a->dbias || bslots));
+    const int st = add_norm_bwd(a, wslots, a->dbias ? bslots : nullptr, stream);
+    if (st != 0) return st;
+    const int n = cad_add_norm_bwd_slots(a);
+    const int sw = cad_reduce_partials(wslots, n, a->D, a->dweight, CAD_F32, stream);
+    if (sw != 0 || !a->dbias) return sw;
+    return cad_reduce_partials(bslots, n, a->D, a->dbias, CAD_F32, stream);
 }

@@ -33,6 +33,8 @@ struct ConvFwdSets {
 };
 struct ConvBwdSets {
     cad_conv1d_bwd_args s[CV_MAXSETS];
+    float* wslots[CV_MAXSETS];  // per-workgroup slots of dw / dbias (cad_conv1d_bwd_multi_slotted), or NULL: fp32 atomics
+    float* bslots[CV_MAXSETS];
 };
 
 template <typename T>
@@ -338,7 +340,7 @@ __global__ __launch_bounds__(CV_THREADS, CV_BWD_WAVES) void conv1d_bwd_kernel(Co
         }
         if (useful != 0.f) store8v<T, VEC>(dx, l0_c, L, o);
     }
-    // workgroup reduction of the dw / dbias partials, then a handful of atomics per workgroup
+    // workgroup reduction of the dw / dbias partials, then a handful of atomics per workgroup (or stores into its slots)
 #pragma unroll
     for (int s = 0; s < NSETS; ++s)
 #pragma unroll
@@ -357,12 +359,18 @@ __global__ __launch_bounds__(CV_THREADS, CV_BWD_WAVES) void conv1d_bwd_kernel(Co
             if (k < a.K) {  // w[k] lives in w4[k + 4 - K]
                 float tot = 0.f;
                 for (int wv = 0; wv < CV_WAVES; ++wv) tot += red[wv][s][k + CV_KMAX - a.K];
-                if (tot != 0.f) atomicAdd(&a.dw[e * a.K + k], tot);
+                if (tot != 0.f) {
+                    if (sets.wslots[s]) sets.wslots[s][(int64_t)blockIdx.y * a.E * a.K + e * a.K + k] = tot;
+                    else atomicAdd(&a.dw[e * a.K + k], tot);
+                }
             }
         } else if (a.dbias) {
             float tot = 0.f;
             for (int wv = 0; wv < CV_WAVES; ++wv) tot += red[wv][s][CV_KMAX];
-            if (tot != 0.f) atomicAdd(&a.dbias[e], tot);
+            if (tot != 0.f) {
+                if (sets.bslots[s]) sets.bslots[s][(int64_t)blockIdx.y * a.E + e] = tot;
+                else atomicAdd(&a.dbias[e], tot);
+            }
         }
     }
 }
@@ -414,9 +422,20 @@ extern "C" int cad_conv1d_fwd_multi(const cad_conv1d_args* sets, int nsets, void
 
 extern "C" int cad_conv1d_fwd(const cad_conv1d_args* a, void* stream) { return cad_conv1d_fwd_multi(a, 1, stream); }
 
-extern "C" int cad_conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, void* stream) {
+extern "C" int cad_conv1d_bwd_slots(const cad_conv1d_bwd_args* a) {  // = the backward grid's workgroups per channel (grid.y)
+    if (!a || a->SB <= 0 || a->L <= 0) return 0;
+    const int64_t nvt = a->SB * ((a->L + CV_WAVE_POS - 1) / CV_WAVE_POS);
+    const int64_t per_block = (int64_t)CV_WAVES * CV_TILES_BWD;
+    return (int)((nvt + per_block - 1) / per_block);
+}
+
+static int conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, float* const* wslots, float* const* bslots, void* stream) {
     CAD_CHECK_ARG(sets && nsets >= 1 && nsets <= CV_MAXSETS);
     ConvBwdSets ks;
+    for (int i = 0; i < CV_MAXSETS; ++i) {
+        ks.wslots[i] = (wslots && i < nsets) ? wslots[i] : nullptr;
+        ks.bslots[i] = (bslots && i < nsets && sets[i].dbias) ? bslots[i] : nullptr;
+    }
     for (int i = 0; i < nsets; ++i) {
         const cad_conv1d_bwd_args* a = &sets[i];
         CAD_CHECK_ARG(a->x && a->w && a->dout && a->dx && a->dw);
@@ -458,6 +477,25 @@ extern "C" int cad_conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, 
     }
 #undef CV_BWD
     return cad_after_launch();
+}
+
+extern "C" int cad_conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, void* stream) {
+    return conv1d_bwd_multi(sets, nsets, nullptr, nullptr, stream);
+}
+
+extern "C" int cad_conv1d_bwd_multi_slotted(const cad_conv1d_bwd_args* sets, int nsets, float* const* wslots, float* const* bslots,
+                                            void* stream) {
+    CAD_CHECK_ARG(sets && nsets >= 1 && nsets <= CV_MAXSETS && wslots && bslots);
+    for (int i = 0; i < nsets; ++i) CAD_CHECK_ARG(wslots[i] && (!sets[i].dbias || bslots[i]));
+    const int st = conv1d_bwd_multi(sets, nsets, wslots, bslots, stream);
+    if (st != 0) return st;
+    const int n = cad_conv1d_bwd_slots(&sets[0]);
+    for (int i = 0; i < nsets; ++i) {
+        int r = cad_reduce_partials(wslots[i], n, (int64_t)sets[i].E * sets[i].K, sets[i].dw, CAD_F32, stream);
+        if (r == 0 && sets[i].dbias) r = cad_reduce_partials(bslots[i], n, sets[i].E, sets[i].dbias, CAD_F32, stream);
+        if (r != 0) return r;
+    }
+    return 0;
 }
 
 extern "C" int cad_conv1d_bwd(const cad_conv1d_bwd_args* a, void* stream) { return cad_conv1d_bwd_multi(a, 1, stream); }

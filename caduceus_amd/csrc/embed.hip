@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * EMB_WAVES) void embed_fwd_vec_kernel(cad_embed
 // in flight under the current one; the four tables are added and flushed with fp32 atomics as below.
 #define EMB_TOK_PER_BLOCK_VEC 256
 template <typename TG>
-__global__ __launch_bounds__(64 * EMB_WAVES) void embed_bwd_vec_kernel(cad_embed_bwd_args a) {
+__global__ __launch_bounds__(64 * EMB_WAVES) void embed_bwd_vec_kernel(cad_embed_bwd_args a, float* slots) {
     CAD_DYN_SMEM(float, acc);  // [EMB_WAVES][V][D]
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -113,7 +113,10 @@ __global__ __launch_bounds__(64 * EMB_WAVES) void embed_bwd_vec_kernel(cad_embed
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < EMB_WAVES; ++w) v += acc[w * VD + i];
-        if (v != 0.f) atomicAdd(&a.dweight[i], v);
+        if (v != 0.f) {
+            if (slots) slots[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * VD + i] = v;
+            else atomicAdd(&a.dweight[i], v);
+        }
     }
 }
 
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(64 * EMB_WAVES) void embed_bwd_vec_kernel(cad_embed
 // no LDS conflicts / atomics), then flushes with fp32 global atomics.
 #define EMB_TOK_PER_BLOCK 512
 template <typename TG>
-__global__ void embed_bwd_kernel(cad_embed_bwd_args a) {
+__global__ void embed_bwd_kernel(cad_embed_bwd_args a, float* slots) {
     CAD_DYN_SMEM(float, acc);
     const int64_t tokens = a.B * a.L;
     const int s = blockIdx.y;
@@ -141,7 +144,10 @@ __global__ void embed_bwd_kernel(cad_embed_bwd_args a) {
     __syncthreads();
     for (int i = threadIdx.x; i < a.V * a.D; i += blockDim.x) {
         const float v = acc[i];
-        if (v != 0.f) atomicAdd(&a.dweight[i], v);
+        if (v != 0.f) {
+            if (slots) slots[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * a.V * a.D + i] = v;
+            else atomicAdd(&a.dweight[i], v);
+        }
     }
 }
 
@@ -180,7 +186,13 @@ extern "C" int cad_embed_fwd(const cad_embed_args* a, void* stream) {
     return cad_after_launch();
 }
 
-extern "C" int cad_embed_bwd(const cad_embed_bwd_args* a, void* stream) {
+// every workgroup of either backward kernel owns one slot; the vector kernel's grid (EMB_TOK_PER_BLOCK_VEC <= EMB_TOK_PER_BLOCK) is the larger
+extern "C" int cad_embed_bwd_slots(const cad_embed_bwd_args* a) {
+    if (!a || a->B <= 0 || a->L <= 0) return 0;
+    return (int)((a->B * a->L + EMB_TOK_PER_BLOCK_VEC - 1) / EMB_TOK_PER_BLOCK_VEC) * a->n_strands;
+}
+
+static int embed_bwd(const cad_embed_bwd_args* a, float* slots, void* stream) {
     CAD_CHECK_ARG(a && a->ids && a->dout && a->dweight);
     CAD_CHECK_ARG(a->B > 0 && a->L > 0 && a->D > 0 && a->V > 0);
     CAD_CHECK_ARG(a->n_strands == 1 || (a->n_strands == 2 && a->comp));
@@ -193,17 +205,26 @@ extern "C" int cad_embed_bwd(const cad_embed_bwd_args* a, void* stream) {
         (a->dout_dtype == CAD_F32 || a->dout_dtype == CAD_BF16)) {
         dim3 gridv((unsigned)((tokens + EMB_TOK_PER_BLOCK_VEC - 1) / EMB_TOK_PER_BLOCK_VEC), (unsigned)a->n_strands), blockv(64 * EMB_WAVES);
         if (a->dout_dtype == CAD_F32)
-            CAD_LAUNCH((embed_bwd_vec_kernel<float>), gridv, blockv, shmem_vec, stream, *a);
+            CAD_LAUNCH((embed_bwd_vec_kernel<float>), gridv, blockv, shmem_vec, stream, *a, slots);
         else
-            CAD_LAUNCH((embed_bwd_vec_kernel<bf16_t>), gridv, blockv, shmem_vec, stream, *a);
+            CAD_LAUNCH((embed_bwd_vec_kernel<bf16_t>), gridv, blockv, shmem_vec, stream, *a, slots);
         return cad_after_launch();
     }
     dim3 grid((unsigned)((tokens + EMB_TOK_PER_BLOCK - 1) / EMB_TOK_PER_BLOCK), (unsigned)a->n_strands), block(256);
     if (a->dout_dtype == CAD_F32)
-        CAD_LAUNCH((embed_bwd_kernel<float>), grid, block, shmem, stream, *a);
+        CAD_LAUNCH((embed_bwd_kernel<float>), grid, block, shmem, stream, *a, slots);
     else if (a->dout_dtype == CAD_BF16)
-        CAD_LAUNCH((embed_bwd_kernel<bf16_t>), grid, block, shmem, stream, *a);
+        CAD_LAUNCH((embed_bwd_kernel<bf16_t>), grid, block, shmem, stream, *a, slots);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
+}
+
+extern "C" int cad_embed_bwd(const cad_embed_bwd_args* a, void* stream) { return embed_bwd(a, nullptr, stream); }
+
+extern "C" int cad_embed_bwd_slotted(const cad_embed_bwd_args* a, float* slots, void* stream) {
+    CAD_CHECK_ARG(a && slots);
+    const int st = embed_bwd(a, slots, stream);
+    if (st != 0) return st;
+    return cad_reduce_partials(slots, cad_embed_bwd_slots(a), (int64_t)a->V * a->D, a->dweight, CAD_F32, stream);
 }

@@ -59,7 +59,7 @@ def _conv_bwd2(x, params, douts, dx, split, dirs, bufs=None):
     E, SB, Lq = x.shape
     n = len(params)
     args = (L.Conv1dBwdArgs * n)()
-    res = []
+    res, slots = [], []
     for i, (wf, bf) in enumerate(params):
         if bufs is not None:
             dw, db = bufs[i]
@@ -69,8 +69,14 @@ def _conv_bwd2(x, params, douts, dx, split, dirs, bufs=None):
         stream = L.stream_and_check(x, wf, bf, douts[i], dx, dw, db)
         args[i] = L.Conv1dBwdArgs(L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(douts[i]), L.ptr(dx), L.ptr(dw), L.ptr(db), SB, Lq,
                                   split, E, wf.shape[1], dirs[i][0], dirs[i][1], L.dtype_code(x.dtype), 0)
+        # per-workgroup slots of dw / dbias, folded by the library in a fixed order (ops.wgrad_slots): the same gradient every run
+        ns = L.get_lib().cad_conv1d_bwd_slots(C.byref(args[i]))
+        ws, bs = ops.wgrad_slots(ns, dw.numel(), x.device), (None if db is None else ops.wgrad_slots(ns, E, x.device))
         res.append((dw, db))
-    L.check(L.get_lib().cad_conv1d_bwd_multi(args, n, stream), "cad_conv1d_bwd_multi")
+        slots.append((ws, bs))
+    wptr = (C.c_void_p * n)(*[ws.data_ptr() for ws, _ in slots])
+    bptr = (C.c_void_p * n)(*[0 if bs is None else bs.data_ptr() for _, bs in slots])
+    L.check(L.get_lib().cad_conv1d_bwd_multi_slotted(args, n, wptr, bptr, stream), "cad_conv1d_bwd_multi_slotted")
     return res
 
 

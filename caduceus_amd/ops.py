@@ -57,8 +57,18 @@ class _Embed(torch.autograd.Function):
         B, Lq = ids.shape
         a = L.EmbedBwdArgs(L.ptr(ids), L.ptr(comp), L.ptr(dout), L.ptr(dw), B, Lq, D, V, n_strands,
                            L.dtype_code(dout.dtype))
-        L.check(L.get_lib().cad_embed_bwd(C.byref(a), stream), "cad_embed_bwd")
+        slots = wgrad_slots(L.get_lib().cad_embed_bwd_slots(C.byref(a)), V * D, dout.device)
+        L.check(L.get_lib().cad_embed_bwd_slotted(C.byref(a), L.ptr(slots), stream), "cad_embed_bwd_slotted")
         return None, dw.to(wdt), None, None, None
+
+
+def wgrad_slots(n_slots: int, n: int, device) -> torch.Tensor:
+    """Zeroed fp32 (n_slots, n): one slot per workgroup of a backward kernel for its share of a weight gradient (the cad_*_bwd_slotted
+    entry points), folded by the library in a fixed order instead of fp32 atomics in arrival order, so that the gradient -- and every
+    training step after it -- is the same in every run."""
+    if n_slots < 1:
+        raise RuntimeError("caduceus_amd: a backward kernel reported no workgroups")
+    return torch.zeros((n_slots, n), dtype=torch.float32, device=device)
 
 
 def embed(ids: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor], n_strands: int,
@@ -122,7 +132,9 @@ class _AddNorm(torch.autograd.Function):
         a = L.AddNormBwdArgs(L.ptr(dy), L.ptr(dres_out), L.ptr(res_out), L.ptr(rstd), L.ptr(mean), L.ptr(w), L.ptr(dx),
                              L.ptr(dres_in), L.ptr(dw), L.ptr(db), rows, S, D, int(is_rms), int(swap_flip),
                              L.dtype_code(x_dtype), L.dtype_code(y_dtype))
-        L.check(L.get_lib().cad_add_norm_bwd(C.byref(a), stream), "cad_add_norm_bwd")
+        n = L.get_lib().cad_add_norm_bwd_slots(C.byref(a))
+        ws, bs = wgrad_slots(n, D, dy.device), (None if db is None else wgrad_slots(n, D, dy.device))
+        L.check(L.get_lib().cad_add_norm_bwd_slotted(C.byref(a), L.ptr(ws), L.ptr(bs), stream), "cad_add_norm_bwd_slotted")
         return dx, dres_in, dw.to(wdt), (None if db is None else db.to(wdt)), None, None, None, None, None
 
 
@@ -197,7 +209,11 @@ class _Conv1d(torch.autograd.Function):
         stream = L.stream_and_check(x, wf, bf, dout, dx, dw, db)
         a = L.Conv1dBwdArgs(L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(dout), L.ptr(dx), L.ptr(dw), L.ptr(db), SB, Lq, split,
                             E, wf.shape[1], rev_lo, rev_hi, L.dtype_code(x.dtype), 0)
-        L.check(L.get_lib().cad_conv1d_bwd(C.byref(a), stream), "cad_conv1d_bwd")
+        n = L.get_lib().cad_conv1d_bwd_slots(C.byref(a))
+        ws, bs = wgrad_slots(n, dw.numel(), x.device), (None if db is None else wgrad_slots(n, E, x.device))
+        L.check(L.get_lib().cad_conv1d_bwd_multi_slotted(C.byref(a), 1, (C.c_void_p * 1)(ws.data_ptr()),
+                                                         (C.c_void_p * 1)(0 if bs is None else bs.data_ptr()), stream),
+                "cad_conv1d_bwd_multi_slotted")
         return dx, dw.reshape(wshape).to(wdt), (None if db is None else db.to(wdt)), None, None, None
 
 

@@ -72,6 +72,11 @@ typedef struct {
     int dout_dtype;
 } cad_embed_bwd_args;
 int cad_embed_bwd(const cad_embed_bwd_args* a, void* stream);
+/* The same backward with a run-to-run identical dW: every workgroup adds its share into a slot of its own instead of fp32 atomics in
+ * arrival order, and the slots are then folded into dweight in a fixed order (cad_reduce_partials, same stream).  dweight is WRITTEN.
+ * slots: cad_embed_bwd_slots(a) x (V, D) fp32, zeroed by the caller. */
+int cad_embed_bwd_slotted(const cad_embed_bwd_args* a, float* slots, void* stream);
+int cad_embed_bwd_slots(const cad_embed_bwd_args* a);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Fused residual-add + RMSNorm / LayerNorm over both strands.   Replaces mamba_ssm rms_norm_fn / layer_norm_fn
@@ -128,6 +133,10 @@ typedef struct {
     int x_dtype, y_dtype;
 } cad_add_norm_bwd_args;
 int cad_add_norm_bwd(const cad_add_norm_bwd_args* a, void* stream);
+/* The same backward with run-to-run identical dweight / dbias (WRITTEN): per-workgroup slots folded in a fixed order, as for
+ * cad_embed_bwd_slotted.  wslots / bslots: cad_add_norm_bwd_slots(a) x (D) fp32 each, zeroed by the caller (bslots iff dbias). */
+int cad_add_norm_bwd_slotted(const cad_add_norm_bwd_args* a, float* wslots, float* bslots, void* stream);
+int cad_add_norm_bwd_slots(const cad_add_norm_bwd_args* a);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Depthwise causal conv1d (+bias, +SiLU) along L, channel-major, with per-row direction.
@@ -169,6 +178,11 @@ typedef struct {
 int cad_conv1d_bwd(const cad_conv1d_bwd_args* a, void* stream);
 /* nsets (1 or 2) parameter sets with the same x, dx and accumulate flag: dx = (accumulate ? dx : 0) + sum over the sets. */
 int cad_conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, void* stream);
+/* The same backward with run-to-run identical dw / dbias of every set (WRITTEN): per-workgroup slots folded in a fixed order, as for
+ * cad_embed_bwd_slotted.  wslots[i] / bslots[i]: cad_conv1d_bwd_slots(&sets[0]) x (E, K) / (E) fp32, zeroed by the caller (bslots[i]
+ * iff sets[i].dbias). */
+int cad_conv1d_bwd_multi_slotted(const cad_conv1d_bwd_args* sets, int nsets, float* const* wslots, float* const* bslots, void* stream);
+int cad_conv1d_bwd_slots(const cad_conv1d_bwd_args* a);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Selective SSM scan, one direction per row.   Replaces selective_scan_cuda.fwd / .bwd reached through

@@ -72,3 +72,21 @@ def test_bench_single_rank_line(tmp_path):
     line = _run(1, [], tmp_path)
     assert line["n_gpus"] == 1 and line["config"]["parallelism"] == "dp1" and line["scaling"] == "weak"
     assert line["dist"]["world_size"] == 1 and line["dist"]["allreduce_exposed_ms_per_step"] is None
+    assert line["roofline"] is None and line["cpu_baseline"] is None  # a plain run takes the headline only (evidence: --full)
+
+
+def test_bench_full_and_dump_outputs(tmp_path):
+    """--full runs the evidence beyond the headline in the same process (on the emulator: the extra untimed step; no device timings);
+    --dump-outputs writes what the last TIMED step computed, float32 .npy files of at most 64 MB in all."""
+    import numpy as np
+    out = tmp_path / "dump"
+    line = _run(1, ["--full", "--dump-outputs", str(out)], tmp_path)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    names = sorted(p.name for p in out.iterdir())
+    assert names == ["grad_norm.npy", "grads.npy", "logits.npy", "loss.npy", "params.npy"], names
+    arrs = {n[:-4]: np.load(out / n) for n in names}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert sum((out / n).stat().st_size for n in names) <= 64_000_000
+    assert arrs["logits"].shape[:2] == (1, 256) and np.isfinite(arrs["logits"]).all()
+    assert arrs["params"].size == arrs["grads"].size == line["config"]["params"]
+    assert float(arrs["loss"]) == line["config"]["final_loss"]  # the timed step's loss, not the one of --full's extra step

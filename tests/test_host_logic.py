@@ -190,12 +190,10 @@ def _locate(dotted):
 
 def test_reference_import_name_resolves_to_this_engine():
     import os
-    ref = "/root/reference"
-    if os.path.isdir(ref):  # build container: take the literal strings from the reference's own files (absent on the GPU box)
-        reg = open(os.path.join(ref, "src", "utils", "registry.py")).read()
-        yml = open(os.path.join(ref, "configs", "model", "caduceus.yaml")).read()
-        assert f'"caduceus_lm": "{REGISTRY_MODEL_STRING}"' in reg
-        assert f"_target_: {HYDRA_CONFIG_TARGET}" in yml
+    # the literal lines of the reference's own files (registry entry, hydra config target), recorded in tests/golden
+    ref = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_import_names.json")))
+    assert f'"caduceus_lm": "{REGISTRY_MODEL_STRING}"' in ref["src/utils/registry.py:29"]
+    assert f"_target_: {HYDRA_CONFIG_TARGET}" in ref["configs/model/caduceus.yaml:4"]
     import caduceus
     import caduceus_amd
     assert _locate(REGISTRY_MODEL_STRING) is caduceus_amd.CaduceusForMaskedLM

@@ -197,3 +197,24 @@ def test_zero_hidden_rows_gate_gradient(backend):
     torch.testing.assert_close(h.detach().cpu(), href.detach(), **FP32)
     scale = max(1.0, float(xr.grad.abs().max()))
     torch.testing.assert_close(x.grad.cpu(), xr.grad, rtol=6e-4, atol=2e-3 * scale)
+
+
+def test_training_step_gradients_repeat_bit_for_bit(backend):
+    """The weight gradients that used to be summed with fp32 atomics in arrival order (embedding, add + norm, conv1d) are folded from
+    per-workgroup slots in a fixed order: the same inputs give bit-identical gradients (Caduceus-PS, batch 1, bf16 as in bench.py)."""
+    kind, dev = backend
+    import bench
+    L = 4096 if kind == "hip" else 512
+    torch.manual_seed(2222)
+    model = CaduceusForMaskedLM(bench.make_config(64, 2)).to(dev).train()
+    ids, labels = bench.synthetic_batch(torch.Generator().manual_seed(7), 1, L, dev)
+    grads = []
+    for _ in range(2):
+        model.zero_grad(set_to_none=True)
+        with torch.autocast(dev.type, dtype=torch.bfloat16):
+            out = model(ids, labels=labels)
+        out.loss.backward()
+        grads.append({n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None})
+    assert grads[0].keys() == grads[1].keys() and len(grads[0]) > 0
+    differ = [n for n in grads[0] if not torch.equal(grads[0][n], grads[1][n])]
+    assert not differ, differ

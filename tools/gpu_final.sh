@@ -30,17 +30,19 @@ PY
 # was busy for, and how much of every kernel ran alone, is the interval union)
 python tools/trace_overlap.py gpurun_out/prof_step/trace 4 > gpurun_out/step_trace_overlap_final.txt 2>&1; head -6 gpurun_out/step_trace_overlap_final.txt | cut -c1-220
 cp gpurun_out/scan_pmc.json profiles/r06_scan_pmc.json  # (on the box: the bench line below quotes the counters taken on THIS build)
-timeout 400 python bench.py > gpurun_out/bench_final.log 2>gpurun_out/bench_final.err; tail -1 gpurun_out/bench_final.log | cut -c1-400
-timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-floor > gpurun_out/bench_final_20steps.log 2>/dev/null; tail -1 gpurun_out/bench_final_20steps.log | cut -c1-200
+# the bench lines below take --full (roofline, arithmetic floor, CPU baseline); their logs go to $BENCH_LOGS
+BENCH_LOGS=${BENCH_LOGS:-bench_logs}; mkdir -p "$BENCH_LOGS"
+timeout 400 python bench.py --full > $BENCH_LOGS/bench_final.log 2>$BENCH_LOGS/bench_final.err; tail -1 $BENCH_LOGS/bench_final.log | cut -c1-400
+timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-floor > $BENCH_LOGS/bench_final_20steps.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_final_20steps.log | cut -c1-200
 if [ "$1" = all ]; then
-timeout 300 python bench.py --model ph --seqlen 1024 --batch 128 --cpu-sample 0 --no-floor > gpurun_out/bench_c2_ph_L1024_b128.log 2>/dev/null; tail -1 gpurun_out/bench_c2_ph_L1024_b128.log | cut -c1-200
-timeout 300 python bench.py --model ph --cpu-sample 0 > gpurun_out/bench_ph_L131072.log 2>/dev/null; tail -1 gpurun_out/bench_ph_L131072.log | cut -c1-200
-timeout 400 python bench.py --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 > gpurun_out/bench_c4shape_bf16_1gpu.log 2>/dev/null; tail -1 gpurun_out/bench_c4shape_bf16_1gpu.log | cut -c1-200
-timeout 400 python bench.py --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 --fp8-proj > gpurun_out/bench_c4shape_fp8_1gpu.log 2>/dev/null; tail -1 gpurun_out/bench_c4shape_fp8_1gpu.log | cut -c1-200
-CADUCEUS_AMD_LIB_OUT_X_PROJ_D512=1 timeout 400 python bench.py --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 --no-floor > gpurun_out/bench_c4shape_bf16_lib_out_x_proj.log 2>/dev/null; tail -1 gpurun_out/bench_c4shape_bf16_lib_out_x_proj.log | cut -c1-200
+timeout 300 python bench.py --full --model ph --seqlen 1024 --batch 128 --cpu-sample 0 --no-floor > $BENCH_LOGS/bench_c2_ph_L1024_b128.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_c2_ph_L1024_b128.log | cut -c1-200
+timeout 300 python bench.py --full --model ph --cpu-sample 0 > $BENCH_LOGS/bench_ph_L131072.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_ph_L131072.log | cut -c1-200
+timeout 400 python bench.py --full --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 > $BENCH_LOGS/bench_c4shape_bf16_1gpu.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_c4shape_bf16_1gpu.log | cut -c1-200
+timeout 400 python bench.py --full --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 --fp8-proj > $BENCH_LOGS/bench_c4shape_fp8_1gpu.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_c4shape_fp8_1gpu.log | cut -c1-200
+CADUCEUS_AMD_LIB_OUT_X_PROJ_D512=1 timeout 400 python bench.py --full --d-model 512 --seqlen 262144 --steps 3 --warmup 1 --cpu-sample 0 --no-floor > $BENCH_LOGS/bench_c4shape_bf16_lib_out_x_proj.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_c4shape_bf16_lib_out_x_proj.log | cut -c1-200
 timeout 900 bash tools/prof_step_c4.sh 2>&1 | grep -v "^W2026" | cut -c1-200 | head -8
-CADUCEUS_DP_FORCE_COLLECTIVE=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --cpu-sample 0 --no-floor > gpurun_out/bench_torchrun_1rank_rccl.log 2>/dev/null; tail -1 gpurun_out/bench_torchrun_1rank_rccl.log | cut -c1-200
-timeout 300 python bench.py --global-batch 8 --steps 2 --warmup 1 --cpu-sample 0 --no-floor > gpurun_out/bench_global_batch8_1gpu.log 2>/dev/null; tail -1 gpurun_out/bench_global_batch8_1gpu.log | cut -c1-200
+CADUCEUS_DP_FORCE_COLLECTIVE=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --full --cpu-sample 0 --no-floor > $BENCH_LOGS/bench_torchrun_1rank_rccl.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_torchrun_1rank_rccl.log | cut -c1-200
+timeout 300 python bench.py --full --global-batch 8 --steps 2 --warmup 1 --cpu-sample 0 --no-floor > $BENCH_LOGS/bench_global_batch8_1gpu.log 2>/dev/null; tail -1 $BENCH_LOGS/bench_global_batch8_1gpu.log | cut -c1-200
 fi
 if [ "$1" = all ]; then
 # the fp32 path: parity, cad_gemm_f32 against hipBLASLt, step traces without a library GEMM

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 tag=$1; shift
 OUT=gpurun_out/prof_step_$tag
 rm -rf $OUT; mkdir -p $OUT
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-floor "$@" > $OUT/trace.log 2>&1
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-floor "$@" > $OUT/trace.log 2>&1
 python - "$OUT" "gpurun_out/step_trace_$tag.txt" "$*" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/trace/**/*kernel_stats.csv", recursive=True)

@@ -8,7 +8,7 @@ for tag in "" "_fp8"; do
   OUT=gpurun_out/prof_step_c4$tag
   rm -rf $OUT; mkdir -p $OUT
   extra=""; [ "$tag" = "_fp8" ] && extra="--fp8-proj"
-  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --d-model 512 --seqlen 262144 --steps 2 --warmup 1 --cpu-sample 0 --no-floor $extra > $OUT/trace.log 2>&1
+  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --full --d-model 512 --seqlen 262144 --steps 2 --warmup 1 --cpu-sample 0 --no-floor $extra > $OUT/trace.log 2>&1
   tail -1 $OUT/trace.log | cut -c1-300
   python - "$OUT" "gpurun_out/step_trace_c4$tag.txt" <<'PY'
 import csv, glob, sys
