@@ -10,10 +10,11 @@ from .modeling_caduceus import (BiMambaWrapper, Caduceus, CaduceusForMaskedLM, C
 from .modeling_rcps import RCPSAddNormWrapper, RCPSEmbedding, RCPSLMHead, RCPSMambaBlock, RCPSWrapper
 from .tokenization_caduceus import CaduceusTokenizer
 from .downstream import DNAEmbeddingModelCaduceus, SequenceDecoder
+from .mamba import fp16_kernels
 
 __all__ = ["DNAEmbeddingModelCaduceus", "SequenceDecoder", "CaduceusConfig", "Caduceus", "CaduceusForMaskedLM", "CaduceusForSequenceClassification",
            "CaduceusTokenizer", "CaduceusMixerModel", "BiMambaWrapper", "create_block", "RCPSEmbedding", "RCPSWrapper",
-           "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "register_auto_classes"]
+           "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "fp16_kernels", "register_auto_classes"]
 
 
 def register_auto_classes():

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # CADUCEUS_AMD_LIB selects another gfx950 build of the same sources (tuning variants); never a different backend
 LIB_PATH = os.environ.get("CADUCEUS_AMD_LIB") or os.path.join(HERE, "libcaduceus_hip.so")
 
-CAD_F32, CAD_BF16 = 0, 1
+CAD_F32, CAD_BF16, CAD_F16 = 0, 1, 2
 PROF_KINDS = ("scan_fwd", "scan_bwd", "conv_fwd", "conv_bwd", "add_norm_fwd", "add_norm_bwd", "embed", "lm_head", "proj")
 
 _p = C.c_void_p
@@ -172,17 +172,22 @@ SYMBOLS = {
     "cad_scan_bwd_gate_fix": (_i, [C.POINTER(ScanBwdArgs), _i, _p]),
     "cad_scan_gate_fix_entries": (_i64, [_i, _i64, _i64]),
     "cad_proj_wxT": (_i, [C.POINTER(ProjArgs), _p]),
+    "cad_proj_wxT_f16": (_i, [C.POINTER(ProjArgs), _p]),
     "cad_proj_supported": (_i, [_i]),
     "cad_proj_wx": (_i, [C.POINTER(ProjArgs), _p]),
+    "cad_proj_wx_f16": (_i, [C.POINTER(ProjArgs), _p]),
     "cad_proj_wx_supported": (_i, [_i, _i64]),
     "cad_proj_wx_thin_supported": (_i, [_i, _i, _i64]),
     "cad_proj_wx_wgrad": (_i, [C.POINTER(ProjArgs), _p]),
+    "cad_proj_wx_wgrad_f16": (_i, [C.POINTER(ProjArgs), _p]),
     "cad_proj_wx_wgrad_supported": (_i, [_i, _i, _i64]),
     "cad_proj_wx_wgrad_partials": (_i, [_i64]),
     "cad_proj_wgrad_only_supported": (_i, [_i, _i, _i64]),
     "cad_proj_xTw": (_i, [C.POINTER(ProjTmArgs), _p]),
+    "cad_proj_xTw_f16": (_i, [C.POINTER(ProjTmArgs), _p]),
     "cad_proj_xTw_supported": (_i, [_i, _i, _i64]),
     "cad_gemm_stream": (_i, [C.POINTER(GemmStreamArgs), _p]),
+    "cad_gemm_stream_f16": (_i, [C.POINTER(GemmStreamArgs), _p]),
     "cad_gemm_stream_supported": (_i, [_i64, _i64, _i64, _i]),
     "cad_fold_f32_multi": (_i, [C.POINTER(FoldF32Job), _i, _p]),
     "cad_gemm_f32": (_i, [C.POINTER(GemmF32Args), _p]),
@@ -271,7 +276,9 @@ def dtype_code(dt: torch.dtype) -> int:
         return CAD_F32
     if dt == torch.bfloat16:
         return CAD_BF16
-    raise TypeError(f"caduceus_amd kernels support float32 and bfloat16 activations, got {dt}")
+    if dt == torch.float16:
+        return CAD_F16
+    raise TypeError(f"caduceus_amd kernels support float32, bfloat16 and float16 activations, got {dt}")
 
 
 def ptr(t):

@@ -27,7 +27,12 @@ class CaduceusConfig(PretrainedConfig):
             complement_map: Optional[dict] = None,
             **kwargs,
     ):
+        # opt-in fp16 kernels (caduceus_amd.fp16_kernels), not a field of the reference: stored only when given, so that configs without
+        # it serialise exactly as before
+        fp16_kernels = kwargs.pop("fp16_kernels", None)
         super().__init__(**kwargs)
+        if fp16_kernels is not None:
+            self.fp16_kernels = bool(fp16_kernels)
         self.d_model = d_model
         self.n_layer = n_layer
         self.vocab_size = vocab_size

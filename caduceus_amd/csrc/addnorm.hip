@@ -196,6 +196,10 @@ __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float* o) {
     o[0] = cad_bits2f(t.w[0] << 16), o[1] = cad_bits2f(t.w[0] & 0xffff0000u);
     o[2] = cad_bits2f(t.w[1] << 16), o[3] = cad_bits2f(t.w[1] & 0xffff0000u);
 }
+template <>
+__device__ __forceinline__ void ld4<f16_t>(const f16_t* p, float* o) {
+    cad_ld4_16<f16_t>(p, o);
+}
 
 // KMAX = 256-channel steps per lane: 1 for D <= 256 (a third of the registers of the general instantiation, twice the waves per
 // SIMD), 2 for D <= 512 (configs[4])
@@ -451,6 +455,10 @@ extern "C" int cad_add_norm_fwd(const cad_add_norm_args* a, void* stream) {
         AN_FWD(float, bf16_t);
     else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
         AN_FWD(bf16_t, bf16_t);
+    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
+        AN_FWD(float, f16_t);
+    else if (a->x_dtype == CAD_F16 && a->y_dtype == CAD_F16)
+        AN_FWD(f16_t, f16_t);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
@@ -497,6 +505,10 @@ static int add_norm_bwd(const cad_add_norm_bwd_args* a, float* wslots, float* bs
         AN_BWD(float, bf16_t);
     else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
         AN_BWD(bf16_t, bf16_t);
+    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
+        AN_BWD(float, f16_t);
+    else if (a->x_dtype == CAD_F16 && a->y_dtype == CAD_F16)
+        AN_BWD(f16_t, f16_t);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();

@@ -86,6 +86,26 @@ __device__ __forceinline__ f32x4 cad_mfma_16x16x32_bf16(u32x4 a, u32x4 b, f32x4 
     return __builtin_bit_cast(f32x4, r);
 }
 
+// v_mfma_f32_16x16x32_f16: the fp16 twin of the above -- same 16 x 16 x 32 shape, same operand packing (8 halves per lane in 4 dwords).
+__device__ __forceinline__ f32x4 cad_mfma_16x16x32_f16(u32x4 a, u32x4 b, f32x4 c) {
+    typedef _Float16 f16x8_hw __attribute__((ext_vector_type(8)));
+    typedef float f32x4_hw __attribute__((ext_vector_type(4)));
+    const f32x4_hw r = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_hw, a), __builtin_bit_cast(f16x8_hw, b),
+                                                              __builtin_bit_cast(f32x4_hw, c), 0, 0, 0);
+    return __builtin_bit_cast(f32x4, r);
+}
+
+// binary16 <-> fp32 through conversions the compiler sees: v_cvt_f16_f32 (round-to-nearest-even in the default mode, +-inf on
+// overflow, NaN stays NaN) and v_cvt_f32_f16 (exact)
+__device__ __forceinline__ uint16_t cad_f32_to_f16(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+__device__ __forceinline__ float cad_f16_to_f32(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ uint32_t cad_pack_f16x2(float lo, float hi) {
+    typedef _Float16 f16x2_hw __attribute__((ext_vector_type(2)));
+    typedef float f32x2_hw __attribute__((ext_vector_type(2)));
+    const f32x2_hw v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_hw));
+}
+
 // v_mfma_f32_16x16x4_f32:  D (16 x 16 fp32) = A (16 x 4 fp32) * B (4 x 16 fp32) + C.  Lane l, g = l >> 4:  A: row l & 15, k = g;
 // B: k = g, column l & 15;  C / D as above (column l & 15, rows 4g + r).  Full fp32 operands: the LM head keeps its fp32 weight.
 __device__ __forceinline__ f32x4 cad_mfma_16x16x4_f32(float a, float b, f32x4 c) {

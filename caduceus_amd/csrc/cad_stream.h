@@ -32,3 +32,7 @@ template <>
 __device__ __forceinline__ void cad_cvt_store_stream<CAD_STREAM_NORM, bf16_t, 4>(bf16_t* dst, const float* v) {
     cad_store_stream<CAD_STREAM_NORM>((u32x2*)dst, u32x2{cad_pack_bf16x2(v[0], v[1]), cad_pack_bf16x2(v[2], v[3])});
 }
+template <>
+__device__ __forceinline__ void cad_cvt_store_stream<CAD_STREAM_NORM, f16_t, 4>(f16_t* dst, const float* v) {
+    cad_store_stream<CAD_STREAM_NORM>((u32x2*)dst, u32x2{cad_pack_f16x2(v[0], v[1]), cad_pack_f16x2(v[2], v[3])});
+}

@@ -15,6 +15,18 @@ typedef uint32_t u32x4 __attribute__((vector_size(16)));
 struct bf16_t {
     uint16_t v;
 };
+struct f16_t {  // IEEE binary16 bits (the opt-in fp16 activations; arithmetic stays fp32)
+    uint16_t v;
+};
+// the bf16-only tricks (bf16 1.0 MFMA selectors, v_perm widening, the packed slab / concurrent fold) test this, not sizeof(T) == 2
+template <typename T>
+struct cad_is_bf16 {
+    static constexpr bool value = false;
+};
+template <>
+struct cad_is_bf16<bf16_t> {
+    static constexpr bool value = true;
+};
 
 __device__ __forceinline__ float cad_bits2f(uint32_t u) {
     union {
@@ -51,4 +63,31 @@ __device__ __forceinline__ bf16_t from_f32<bf16_t>(float f) {  // round-to-neare
         r.v = (uint16_t)(u >> 16);
     }
     return r;
+}
+
+// binary16 <-> fp32 in plain C++ (the host emulator's conversion; the device uses v_cvt_f16_f32 / v_cvt_f32_f16 behind the primitives
+// seam).  Round-to-nearest-even; beyond 65504 (after rounding) +-inf, never saturated; NaN stays NaN (quiet, sign kept); subnormals exact.
+// Float-arithmetic formulation of the FP16 library (Maratyszcza, MIT): the scaled add rounds the mantissa in the FPU.
+__device__ __forceinline__ uint16_t cad_f32_to_f16_soft(float f) {
+    const float scale_to_inf = cad_bits2f(0x77800000u);   // 2^112
+    const float scale_to_zero = cad_bits2f(0x08800000u);  // 2^-110
+    const uint32_t w = cad_f2bits(f);
+    const uint32_t shl1_w = w + w;
+    const uint32_t sign = w & 0x80000000u;
+    float base = (cad_bits2f(w & 0x7fffffffu) * scale_to_inf) * scale_to_zero;
+    uint32_t bias = shl1_w & 0xff000000u;
+    if (bias < 0x71000000u) bias = 0x71000000u;
+    base = cad_bits2f((bias >> 1) + 0x07800000u) + base;
+    const uint32_t bits = cad_f2bits(base);
+    const uint32_t nonsign = ((bits >> 13) & 0x00007c00u) + (bits & 0x00000fffu);
+    return (uint16_t)((sign >> 16) | (shl1_w > 0xff000000u ? 0x7e00u : nonsign));
+}
+__device__ __forceinline__ float cad_f16_to_f32_soft(uint16_t h) {
+    const uint32_t w = (uint32_t)h << 16;
+    const uint32_t sign = w & 0x80000000u;
+    const uint32_t two_w = w + w;
+    const float normalized = cad_bits2f((two_w >> 4) + 0x70000000u) * cad_bits2f(0x07800000u);  // exponent offset (0xE0 << 23), 2^-112
+    const float denormalized = cad_bits2f((two_w >> 17) | 0x3f000000u) - 0.5f;
+    const uint32_t r = two_w < (1u << 27) ? cad_f2bits(denormalized) : cad_f2bits(normalized);
+    return cad_bits2f(sign | r);
 }

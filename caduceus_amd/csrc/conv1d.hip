@@ -76,8 +76,8 @@ __device__ __forceinline__ void cvt8(const CvRaw<T>& r, int64_t l0, int64_t L, f
     if constexpr (sizeof(T) == 2) {
 #pragma unroll
         for (int j = 0; j < CV_VEC / 2; ++j) {
-            out[2 * j] = inside ? cad_bits2f(r.w[j] << 16) : 0.f;
-            out[2 * j + 1] = inside ? cad_bits2f(r.w[j] & 0xffff0000u) : 0.f;
+            out[2 * j] = inside ? cad_lo2f<T>(r.w[j]) : 0.f;
+            out[2 * j + 1] = inside ? cad_hi2f<T>(r.w[j]) : 0.f;
         }
     } else {
 #pragma unroll
@@ -413,6 +413,8 @@ extern "C" int cad_conv1d_fwd_multi(const cad_conv1d_args* sets, int nsets, void
         if (nsets == 1) CV_FWD(float, 1); else CV_FWD(float, 2);
     } else if (a->dtype == CAD_BF16) {
         if (nsets == 1) CV_FWD(bf16_t, 1); else CV_FWD(bf16_t, 2);
+    } else if (a->dtype == CAD_F16) {
+        if (nsets == 1) CV_FWD(f16_t, 1); else CV_FWD(f16_t, 2);
     } else {
         return CAD_ERR_UNSUPPORTED;
     }
@@ -472,6 +474,8 @@ static int conv1d_bwd_multi(const cad_conv1d_bwd_args* sets, int nsets, float* c
         if (nsets == 1) CV_BWD(float, 1); else CV_BWD(float, 2);
     } else if (a->dtype == CAD_BF16) {
         if (nsets == 1) CV_BWD(bf16_t, 1); else CV_BWD(bf16_t, 2);
+    } else if (a->dtype == CAD_F16) {
+        if (nsets == 1) CV_BWD(f16_t, 1); else CV_BWD(f16_t, 2);
     } else {
         return CAD_ERR_UNSUPPORTED;
     }

@@ -19,6 +19,10 @@ __device__ __forceinline__ void ld4e<bf16_t>(const bf16_t* p, float* o) {
     o[0] = cad_bits2f(t.w[0] << 16), o[1] = cad_bits2f(t.w[0] & 0xffff0000u);
     o[2] = cad_bits2f(t.w[1] << 16), o[3] = cad_bits2f(t.w[1] & 0xffff0000u);
 }
+template <>
+__device__ __forceinline__ void ld4e<f16_t>(const f16_t* p, float* o) {
+    cad_ld4_16<f16_t>(p, o);
+}
 
 template <typename TW, typename TO>
 __global__ void embed_fwd_kernel(cad_embed_args a) {
@@ -159,14 +163,16 @@ extern "C" int cad_embed_fwd(const cad_embed_args* a, void* stream) {
     CAD_CHECK_ARG(a->n_strands == 1 || (a->n_strands == 2 && a->comp));
     CadProfScope prof(6, stream);
     if (a->w_dtype == CAD_F32 && (a->D % 4) == 0 && (((uintptr_t)a->weight | (uintptr_t)a->out) % 16) == 0 &&
-        (a->out_dtype == CAD_F32 || a->out_dtype == CAD_BF16)) {
+        (a->out_dtype == CAD_F32 || a->out_dtype == CAD_BF16 || a->out_dtype == CAD_F16)) {
         int64_t nbv = (a->B * a->L + EMB_WAVES - 1) / EMB_WAVES;
         if (nbv > 8192) nbv = 8192;
         dim3 gridv((unsigned)nbv), blockv(64 * EMB_WAVES);
         if (a->out_dtype == CAD_F32)
             CAD_LAUNCH((embed_fwd_vec_kernel<float>), gridv, blockv, 0, stream, *a);
-        else
+        else if (a->out_dtype == CAD_BF16)
             CAD_LAUNCH((embed_fwd_vec_kernel<bf16_t>), gridv, blockv, 0, stream, *a);
+        else
+            CAD_LAUNCH((embed_fwd_vec_kernel<f16_t>), gridv, blockv, 0, stream, *a);
         return cad_after_launch();
     }
     const int64_t total = a->B * a->L * a->D * a->n_strands;
@@ -181,6 +187,10 @@ extern "C" int cad_embed_fwd(const cad_embed_args* a, void* stream) {
         CAD_LAUNCH((embed_fwd_kernel<bf16_t, bf16_t>), grid, block, 0, stream, *a);
     else if (a->w_dtype == CAD_BF16 && a->out_dtype == CAD_F32)
         CAD_LAUNCH((embed_fwd_kernel<bf16_t, float>), grid, block, 0, stream, *a);
+    else if (a->w_dtype == CAD_F32 && a->out_dtype == CAD_F16)
+        CAD_LAUNCH((embed_fwd_kernel<float, f16_t>), grid, block, 0, stream, *a);
+    else if (a->w_dtype == CAD_F16 && a->out_dtype == CAD_F16)
+        CAD_LAUNCH((embed_fwd_kernel<f16_t, f16_t>), grid, block, 0, stream, *a);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
@@ -202,12 +212,14 @@ static int embed_bwd(const cad_embed_bwd_args* a, float* slots, void* stream) {
     const int64_t tokens = a->B * a->L;
     const size_t shmem_vec = shmem * EMB_WAVES;
     if ((a->D % 4) == 0 && shmem_vec <= 64 * 1024 && ((uintptr_t)a->dout % 16) == 0 &&
-        (a->dout_dtype == CAD_F32 || a->dout_dtype == CAD_BF16)) {
+        (a->dout_dtype == CAD_F32 || a->dout_dtype == CAD_BF16 || a->dout_dtype == CAD_F16)) {
         dim3 gridv((unsigned)((tokens + EMB_TOK_PER_BLOCK_VEC - 1) / EMB_TOK_PER_BLOCK_VEC), (unsigned)a->n_strands), blockv(64 * EMB_WAVES);
         if (a->dout_dtype == CAD_F32)
             CAD_LAUNCH((embed_bwd_vec_kernel<float>), gridv, blockv, shmem_vec, stream, *a, slots);
-        else
+        else if (a->dout_dtype == CAD_BF16)
             CAD_LAUNCH((embed_bwd_vec_kernel<bf16_t>), gridv, blockv, shmem_vec, stream, *a, slots);
+        else
+            CAD_LAUNCH((embed_bwd_vec_kernel<f16_t>), gridv, blockv, shmem_vec, stream, *a, slots);
         return cad_after_launch();
     }
     dim3 grid((unsigned)((tokens + EMB_TOK_PER_BLOCK - 1) / EMB_TOK_PER_BLOCK), (unsigned)a->n_strands), block(256);
@@ -215,6 +227,8 @@ static int embed_bwd(const cad_embed_bwd_args* a, float* slots, void* stream) {
         CAD_LAUNCH((embed_bwd_kernel<float>), grid, block, shmem, stream, *a, slots);
     else if (a->dout_dtype == CAD_BF16)
         CAD_LAUNCH((embed_bwd_kernel<bf16_t>), grid, block, shmem, stream, *a, slots);
+    else if (a->dout_dtype == CAD_F16)
+        CAD_LAUNCH((embed_bwd_kernel<f16_t>), grid, block, shmem, stream, *a, slots);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();

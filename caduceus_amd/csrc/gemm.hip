@@ -15,12 +15,24 @@
 //     16-byte stores.
 // The per-token arithmetic is independent of the token's position (fixed k order inside the MFMA), so both strands and
 // both directions of the t-frame get bit-identical projections: RC-equivariance stays exact.
+// The bf16 entry points are defined here; the fp16 siblings (cad_*_f16) in gemm_f16.hip, which includes this file with
+// CAD_GEMM_TEMPLATES_ONLY: the kernel templates are element-type templates, each translation unit instantiates one element type.
 #include "cad_common.h"
 #include "cad_stream.h"
 
 namespace {
 
 #define GP_WAVES 8
+
+// the softplus + bias epilogue of dt_proj: bf16 results take the two-transcendental form (cad_softplus_lowp: exact far inside bf16's
+// 8 bits); fp16's 11 bits take the full-accuracy form
+template <typename TE>
+__device__ __forceinline__ float gp_softplus(float x) {
+    if constexpr (cad_is_bf16<TE>::value)
+        return cad_softplus_lowp(x);
+    else
+        return cad_softplus(x);
+}
 
 // K = 512 (d_model 512, configs[4]) tuning knobs: W rows per wave / tokens per block / register double-buffering of the A fragments
 #ifndef GP_MB16
@@ -48,8 +60,8 @@ struct GpCfg {
 };
 
 // issue the LDS-DMA of one NT-token block of X (tokens t0 .. t0 + NT - 1; rows beyond T re-read row T - 1, never stored)
-template <int KS>
-__device__ __forceinline__ void gp_issue_block(const bf16_t* X, int64_t ldx, int64_t t0, int64_t T, char* xbuf, int wave, int lane) {
+template <int KS, typename TE>
+__device__ __forceinline__ void gp_issue_block(const TE* X, int64_t ldx, int64_t t0, int64_t T, char* xbuf, int wave, int lane) {
     typedef GpCfg<KS> C;
     constexpr int PIECES = C::NT * C::PPR;           // per block
     constexpr int INSTR = PIECES / 64;               // DMA instructions per block (64 pieces each)
@@ -70,16 +82,16 @@ __device__ __forceinline__ void gp_issue_block(const bf16_t* X, int64_t ldx, int
 
 __device__ __forceinline__ void gp_wait_dma() { cad_wait_vmcnt<0>(); }
 
-template <int KS>
+template <typename TE, int KS>
 __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wxT_kernel(cad_proj_args a) {
     typedef GpCfg<KS> C;
     CAD_DYN_SMEM(char, smem);
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
     const int g = lane >> 4, jl = lane & 15;
-    const bf16_t* W = (const bf16_t*)a.W;
-    const bf16_t* X = (const bf16_t*)a.X;
-    bf16_t* out = (bf16_t*)a.out;
+    const TE* W = (const TE*)a.W;
+    const TE* X = (const TE*)a.X;
+    TE* out = (TE*)a.out;
     const int64_t T = a.T;
     const int M = a.M;
     const int m_wave = blockIdx.y * C::MWG + wave * C::MW;  // first output channel of this wave
@@ -141,14 +153,14 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wxT_kernel(cad_proj_arg
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-                for (int mb = 0; mb < C::MB; ++mb) d[mb] = cad_mfma_16x16x32_bf16(xf[ks], wf[mb][ks], d[mb]);
+                for (int mb = 0; mb < C::MB; ++mb) d[mb] = cad_mfma_16x16x32<TE>(xf[ks], wf[mb][ks], d[mb]);
             }
             // lane (m = mb * 16 + jl, g) holds tokens 16 q + 4 g .. + 3 of channel m: 8 bytes into the staging tile
 #pragma unroll
             for (int mb = 0; mb < C::MB; ++mb) {
                 u32x2 pk;
-                pk[0] = cad_pack_bf16x2_safe(d[mb][0], d[mb][1]);
-                pk[1] = cad_pack_bf16x2_safe(d[mb][2], d[mb][3]);
+                pk[0] = cad_pack2_safe<TE>(d[mb][0], d[mb][1]);
+                pk[1] = cad_pack2_safe<TE>(d[mb][2], d[mb][3]);
                 *(u32x2*)(stage + (mb * 16 + jl) * C::SSTR + (q * 16 + g * 4) * 2) = pk;
             }
         }
@@ -182,7 +194,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wxT_kernel(cad_proj_arg
                 const int m = m_wave + r;
                 const int64_t t = t0 + c8 * 8;
                 if (m < M) {
-                    bf16_t* dst = out + (int64_t)m * a.ldo + t;
+                    TE* dst = out + (int64_t)m * a.ldo + t;
                     if (t + 8 <= T && (((uintptr_t)dst) & 15) == 0) {
                         *(u32x4*)dst = v;
                     } else {
@@ -217,8 +229,8 @@ struct GxCfg {
 };
 __device__ __forceinline__ int gx_swz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
 
-template <int KS>
-__device__ __forceinline__ void gx_issue_block(const bf16_t* X, int64_t ldx, int K, int64_t t0, int64_t T, char* xbuf,
+template <int KS, typename TE>
+__device__ __forceinline__ void gx_issue_block(const TE* X, int64_t ldx, int K, int64_t t0, int64_t T, char* xbuf,
                                                int wave, int lane) {
     const int ninstr = K / 8;  // K rows x 8 pieces of 16 bytes, 64 pieces per DMA instruction
     for (int ins = wave; ins < ninstr; ins += GP_WAVES) {  // wave-uniform
@@ -231,17 +243,17 @@ __device__ __forceinline__ void gx_issue_block(const bf16_t* X, int64_t ldx, int
     }
 }
 
-template <int KS, bool ACC>
+template <typename TE, int KS, bool ACC>
 __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wx_kernel(cad_proj_args a) {
     typedef GxCfg<KS> C;
     CAD_DYN_SMEM(char, smem);
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
     const int g = lane >> 4, jl = lane & 15;
-    const bf16_t* W = (const bf16_t*)a.W;
-    const bf16_t* X = (const bf16_t*)a.X;
-    const bf16_t* acc = (const bf16_t*)a.acc;
-    bf16_t* out = (bf16_t*)a.out;
+    const TE* W = (const TE*)a.W;
+    const TE* X = (const TE*)a.X;
+    const TE* acc = (const TE*)a.acc;
+    TE* out = (TE*)a.out;
     const int64_t T = a.T;
     const int M = a.M, K = a.K;
     const int m_wave = blockIdx.y * C::MWG + wave * C::MW;
@@ -316,19 +328,19 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wx_kernel(cad_proj_args
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-                for (int mb = 0; mb < C::MB; ++mb) d[mb] = cad_mfma_16x16x32_bf16(xf[ks], wf[mb][ks], d[mb]);
+                for (int mb = 0; mb < C::MB; ++mb) d[mb] = cad_mfma_16x16x32<TE>(xf[ks], wf[mb][ks], d[mb]);
             }
             if (act_sp) {
 #pragma unroll
                 for (int mb = 0; mb < C::MB; ++mb)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) d[mb][r] = cad_softplus_lowp(d[mb][r] + brow[mb]);
+                    for (int r = 0; r < 4; ++r) d[mb][r] = gp_softplus<TE>(d[mb][r] + brow[mb]);
             }
 #pragma unroll
             for (int mb = 0; mb < C::MB; ++mb) {
                 u32x2 pk;
-                pk[0] = cad_pack_bf16x2_safe(d[mb][0], d[mb][1]);
-                pk[1] = cad_pack_bf16x2_safe(d[mb][2], d[mb][3]);
+                pk[0] = cad_pack2_safe<TE>(d[mb][0], d[mb][1]);
+                pk[1] = cad_pack2_safe<TE>(d[mb][2], d[mb][3]);
                 *(u32x2*)(stage + (mb * 16 + jl) * C::SSTR + (q * 16 + g * 4) * 2) = pk;
             }
         }
@@ -345,9 +357,9 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_wx_kernel(cad_proj_args
                 const u32x4 o = old[r0 / RPI];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = cad_bits2f(v[e] << 16) + cad_bits2f(o[e] << 16);
-                    const float hi = cad_bits2f(v[e] & 0xFFFF0000u) + cad_bits2f(o[e] & 0xFFFF0000u);
-                    v[e] = cad_pack_bf16x2(lo, hi);
+                    const float lo = cad_lo2f<TE>(v[e]) + cad_lo2f<TE>(o[e]);
+                    const float hi = cad_hi2f<TE>(v[e]) + cad_hi2f<TE>(o[e]);
+                    v[e] = cad_pack2<TE>(lo, hi);
                 }
             }
             if (m < M && t + 8 <= T) cad_store_stream<CAD_STREAM_PROJ>((u32x4*)(out + (int64_t)m * a.ldo + t), v);
@@ -374,7 +386,8 @@ struct GtCfg {
 static_assert(GtCfg::DPW == 2, "the counted waits below assume two DMA instructions per wave and chunk");
 static_assert((GtCfg::RING & (GtCfg::RING - 1)) == 0, "ring slots are advanced with a mask");
 
-__device__ __forceinline__ void gt_issue_chunk(const bf16_t* X, int64_t ldx, int k0, int64_t t0, int64_t T, char* xbuf, int wave,
+template <typename TE>
+__device__ __forceinline__ void gt_issue_chunk(const TE* X, int64_t ldx, int k0, int64_t t0, int64_t T, char* xbuf, int wave,
                                                int lane) {
 #pragma unroll
     for (int i = 0; i < GtCfg::DPW; ++i) {
@@ -388,16 +401,16 @@ __device__ __forceinline__ void gt_issue_chunk(const bf16_t* X, int64_t ldx, int
     }
 }
 
-template <int MB>
+template <typename TE, int MB>
 __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_kernel(cad_proj_args a) {
     typedef GtCfg C;
     CAD_DYN_SMEM(char, smem);
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
     const int g = lane >> 4, jl = lane & 15;
-    const bf16_t* W = (const bf16_t*)a.W;
-    const bf16_t* X = (const bf16_t*)a.X;
-    bf16_t* out = (bf16_t*)a.out;
+    const TE* W = (const TE*)a.W;
+    const TE* X = (const TE*)a.X;
+    TE* out = (TE*)a.out;
     const int64_t T = a.T;
     const int M = a.M, K = a.K;
     const int NCH = K / C::KC;
@@ -457,25 +470,25 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_kernel(cad_proj
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const u32x4 wf = *(const u32x4*)(wl + (mb * 16 + jl) * WSTR + (ch * C::KC + ks * 32 + g * 8) * 2);
-                d[mb] = cad_mfma_16x16x32_bf16(xf, wf, d[mb]);
+                d[mb] = cad_mfma_16x16x32<TE>(xf, wf, d[mb]);
             }
         }
         slot = (slot + 1) & (C::RING - 1);
         if (++ch == NCH) {
             const int64_t t = blk * C::NT + wave * 16 + g * 4;  // this lane's four consecutive tokens
-            const bf16_t* acc = (const bf16_t*)a.acc;  // wave-uniform: the other K half of a product too deep for one W copy in LDS
+            const TE* acc = (const TE*)a.acc;  // wave-uniform: the other K half of a product too deep for one W copy in LDS
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const int m = mb * 16 + jl;
                 f32x4 v = d[mb];
                 if (acc && m < M && t + 4 <= T) {  // out = bf16(acc + the fp32 sums): the addend is widened, the sum rounded once
                     const u32x2 o = *(const u32x2*)(acc + (int64_t)m * a.ldacc + t);
-                    v[0] += cad_bits2f(o[0] << 16), v[1] += cad_bits2f(o[0] & 0xFFFF0000u);
-                    v[2] += cad_bits2f(o[1] << 16), v[3] += cad_bits2f(o[1] & 0xFFFF0000u);
+                    v[0] += cad_lo2f<TE>(o[0]), v[1] += cad_hi2f<TE>(o[0]);
+                    v[2] += cad_lo2f<TE>(o[1]), v[3] += cad_hi2f<TE>(o[1]);
                 }
                 u32x2 pk;
-                pk[0] = cad_pack_bf16x2_safe(v[0], v[1]);
-                pk[1] = cad_pack_bf16x2_safe(v[2], v[3]);
+                pk[0] = cad_pack2_safe<TE>(v[0], v[1]);
+                pk[1] = cad_pack2_safe<TE>(v[2], v[3]);
                 if (m < M && t + 4 <= T) *(u32x2*)(out + (int64_t)m * a.ldo + t) = pk;
             }
             ch = 0;
@@ -496,17 +509,17 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_kernel(cad_proj
 // of every chunk and the token half w >> 2; the halves are summed through LDS at the end and the workgroup writes its (K, M) fp32
 // partial slot; the caller sums the <= 256 slots (fixed order).
 // PROD = false: the weight gradient alone (a.W / a.out unused) -- dW_x = xc . d(dbc)^T of the x_proj backward (M = dt_rank + 2 d_state).
-template <int MB, int NCH, bool PROD>
+template <typename TE, int MB, int NCH, bool PROD>
 __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(cad_proj_args a) {
     typedef GtCfg C;
     CAD_DYN_SMEM(char, smem);
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
     const int g = lane >> 4, jl = lane & 15;
-    const bf16_t* W = (const bf16_t*)a.W;
-    const bf16_t* X = (const bf16_t*)a.X;
-    const bf16_t* Y = (const bf16_t*)a.wg_y;
-    bf16_t* out = (bf16_t*)a.out;
+    const TE* W = (const TE*)a.W;
+    const TE* X = (const TE*)a.X;
+    const TE* Y = (const TE*)a.wg_y;
+    TE* out = (TE*)a.out;
     const int64_t T = a.T;
     const int M = a.M;
     constexpr int K = NCH * C::KC;
@@ -586,7 +599,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) {
                     const u32x4 wf = *(const u32x4*)(wl + (mb * 16 + jl) * WSTR + (ch * C::KC + ks * 32 + g * 8) * 2);
-                    d[mb] = cad_mfma_16x16x32_bf16(xf, wf, d[mb]);
+                    d[mb] = cad_mfma_16x16x32<TE>(xf, wf, d[mb]);
                 }
             }
             }
@@ -602,7 +615,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
                 for (int mb = 0; mb < MB; ++mb) {
                     const int yr = mb * 16 + jl;
                     const u32x4 bf = *(const u32x4*)(ytile + yr * C::XROW + ((lp ^ (yr & 15)) * 16));
-                    dw[ch][mb] = cad_mfma_16x16x32_bf16(af, bf, dw[ch][mb]);
+                    dw[ch][mb] = cad_mfma_16x16x32<TE>(af, bf, dw[ch][mb]);
                 }
             }
             if (PROD && ch == NCH - 1) {
@@ -612,8 +625,8 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
                 for (int mb = 0; mb < MB; ++mb) {
                     const int m = mb * 16 + jl;
                     u32x2 pk;
-                    pk[0] = cad_pack_bf16x2_safe(d[mb][0], d[mb][1]);
-                    pk[1] = cad_pack_bf16x2_safe(d[mb][2], d[mb][3]);
+                    pk[0] = cad_pack2_safe<TE>(d[mb][0], d[mb][1]);
+                    pk[1] = cad_pack2_safe<TE>(d[mb][2], d[mb][3]);
                     if (m < M) *(u32x2*)(out + (int64_t)m * a.ldo + t) = pk;
                 }
             }
@@ -665,15 +678,15 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
 #ifndef GP_XTW_KS_OUTER
 #define GP_XTW_KS_OUTER 1
 #endif
-template <int MB, int KS>
+template <typename TE, int MB, int KS>
 __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_args a) {
     typedef GtCfg C;
     CAD_DYN_SMEM(char, smem);
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
     const int g = lane >> 4, jl = lane & 15;
-    const bf16_t* W = (const bf16_t*)a.W;
-    bf16_t* out = (bf16_t*)a.out;
+    const TE* W = (const TE*)a.W;
+    TE* out = (TE*)a.out;
     const int64_t T = a.T;
     const int M = a.M;
     constexpr int NCH = KS / 2;                       // 64-row chunks per panel
@@ -692,7 +705,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
     int ich = 0, ipan = 0, islot = 0;
     int64_t iblk = b0;
     auto issue_next = [&]() {
-        gt_issue_chunk((const bf16_t*)(ipan ? a.X2 : a.X), a.ldx, ich * C::KC, iblk * C::NT, T, smem + islot * C::XBUF, wave, lane);
+        gt_issue_chunk((const TE*)(ipan ? a.X2 : a.X), a.ldx, ich * C::KC, iblk * C::NT, T, smem + islot * C::XBUF, wave, lane);
         islot = (islot + 1) & (XR - 1);
         if (++ich == NCH) {
             ich = 0;
@@ -758,7 +771,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
                         const u32x2 lo = cad_lds_read_tr16(p0), hi = cad_lds_read_tr16(p1);
                         const u32x4 xf = {lo[0], lo[1], hi[0], hi[1]};
 #pragma unroll
-                        for (int mb = 0; mb < MB; ++mb) d[q][mb] = cad_mfma_16x16x32_bf16(wf[mb][ch * 2 + ks], xf, d[q][mb]);
+                        for (int mb = 0; mb < MB; ++mb) d[q][mb] = cad_mfma_16x16x32<TE>(wf[mb][ch * 2 + ks], xf, d[q][mb]);
                     }
                 }
             }
@@ -771,8 +784,8 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
             for (int mb = 0; mb < MB; ++mb) {
                 const int m = m_wave + mb * 16 + g * 4;
                 u32x2 pk;
-                pk[0] = cad_pack_bf16x2_safe(d[q][mb][0], d[q][mb][1]);
-                pk[1] = cad_pack_bf16x2_safe(d[q][mb][2], d[q][mb][3]);
+                pk[0] = cad_pack2_safe<TE>(d[q][mb][0], d[q][mb][1]);
+                pk[1] = cad_pack2_safe<TE>(d[q][mb][2], d[q][mb][3]);
                 // (every lane issues the store: the counted waits above rely on exactly NST store instructions per block; lanes of a tail
                 // block / beyond M are masked off by the exec mask, the instruction still counts)
                 if (t < T && m + 4 <= M) {
@@ -838,7 +851,8 @@ static_assert(GP_WAVES == 8, "cad_gemm_stream: 2 x 4 waves per tile, two DMA ins
 // eight consecutive rows x one 16-byte piece (what eight lanes of a ds_read_b128 touch) fall into eight different 16-byte bank groups
 __device__ __forceinline__ int gs_aswz(int row) { return (row >> 1) & 3; }
 
-__device__ __forceinline__ void gs_issue_chunk(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int64_t k0, char* stage,
+template <typename TE>
+__device__ __forceinline__ void gs_issue_chunk(const TE* A, int64_t lda, const TE* B, int64_t ldb, int64_t k0, char* stage,
                                                int wave, int lane) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {  // A: 16 instructions of 16 rows x 4 pieces
@@ -857,7 +871,7 @@ __device__ __forceinline__ void gs_issue_chunk(const bf16_t* A, int64_t lda, con
     }
 }
 
-template <int MODE>
+template <int MODE, typename TE>
 __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_stream_args a) {
     typedef GsCfg C;
     CAD_DYN_SMEM(char, smem);
@@ -897,7 +911,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
     // issue cursor
     int ich = 0, islot = 0;
     int64_t iitem = i0;
-    const bf16_t *iA = nullptr, *iB = nullptr;
+    const TE *iA = nullptr, *iB = nullptr;
     // GS_SLICE_INTERLEAVE (weight-gradient mode, nslices > 1): slice s takes the 32-k chunks s, s + nslices, s + 2 nslices, ... of the
     // reduction range instead of one contiguous k range, so that the workgroups running side by side read NEIGHBOURING 64-byte pieces of
     // the same strided rows (one DRAM page serves them all) instead of 64 bytes each from pages 8 KB apart
@@ -910,8 +924,8 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
         int64_t rt, ct, sl;
         decode(iitem, rt, ct, sl);
         const int64_t kbase = (GS_SLICE_INTERLEAVE && a.nslices > 1) ? sl * C::KC : sl * kper;
-        iA = (const bf16_t*)a.A + rt * C::RT * a.lda + kbase;
-        iB = (const bf16_t*)a.B + kbase * a.ldb + ct * C::CT;
+        iA = (const TE*)a.A + rt * C::RT * a.lda + kbase;
+        iB = (const TE*)a.B + kbase * a.ldb + ct * C::CT;
         irot = (GS_SLICE_ROTATE && a.nslices > 1) ? (int)((sl * GS_ROT_SL + rt * GS_ROT_RT) % nk) : 0;
     };
     seek();
@@ -976,7 +990,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
                 const u32x4 af = (GS_WHATIF & 4) ? u32x4{(uint32_t)(lane ^ i), 0x3f803f80u, (uint32_t)it, 0u}
                                                   : *(const u32x4*)(st + a_off + i * 16 * C::AROW);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = cad_mfma_16x16x32_bf16(af, bfr[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) acc[i][j] = cad_mfma_16x16x32<TE>(af, bfr[j], acc[i][j]);
             }
         }
         int64_t rt, ct, sl;
@@ -993,14 +1007,14 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dst[(int64_t)(16 * i + r) * a.C + 16 * j] = acc[i][j][r];
         } else {
-            bf16_t* dst = (bf16_t*)a.out + col * a.ldo + row;
+            TE* dst = (TE*)a.out + col * a.ldo + row;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     u32x2 pk;
-                    pk[0] = cad_pack_bf16x2_safe(acc[i][j][0], acc[i][j][1]);
-                    pk[1] = cad_pack_bf16x2_safe(acc[i][j][2], acc[i][j][3]);
+                    pk[0] = cad_pack2_safe<TE>(acc[i][j][0], acc[i][j][1]);
+                    pk[1] = cad_pack2_safe<TE>(acc[i][j][2], acc[i][j][3]);
                     *(u32x2*)(dst + (int64_t)(16 * j) * a.ldo + 16 * i) = pk;
                 }
         }
@@ -1013,9 +1027,11 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
 
 #define GP_BIG_LDS(kern, bytes) CAD_BIG_LDS(kern, bytes)  // (cad_prims_gfx950.h)
 
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_supported(int K) { return K == 32 || K == 64 || K == 128 || K == 256 || K == 512; }
+#endif
 
-template <int KS>
+template <typename TE, int KS>
 static int launch_wxT(const cad_proj_args* a, void* stream) {
     typedef GpCfg<KS> C;
     const int64_t nblk = (a->T + C::NT - 1) / C::NT;
@@ -1024,28 +1040,32 @@ static int launch_wxT(const cad_proj_args* a, void* stream) {
     if (gx < 1) gx = 1;
     if (gx > nblk) gx = nblk;
     dim3 grid((unsigned)gx, (unsigned)my), block(64 * GP_WAVES);
-    GP_BIG_LDS((proj_wxT_kernel<KS>), C::LDS);
-    CAD_LAUNCH((proj_wxT_kernel<KS>), grid, block, C::LDS, stream, *a);
+    GP_BIG_LDS((proj_wxT_kernel<TE, KS>), C::LDS);
+    CAD_LAUNCH((proj_wxT_kernel<TE, KS>), grid, block, C::LDS, stream, *a);
     return cad_after_launch();
 }
 
-extern "C" int cad_proj_wxT(const cad_proj_args* a, void* stream) {
+template <typename TE>
+static int proj_wxT(const cad_proj_args* a, void* stream) {
     CAD_CHECK_ARG(a && a->W && a->X && a->out && a->T > 0 && a->M > 0 && a->K > 0 && a->act == 0);
     CAD_CHECK_ARG(a->ldw >= a->K && a->ldx >= a->K && a->ldo >= a->T);
     CAD_CHECK_ARG((a->ldw % 8) == 0 && (a->ldx % 8) == 0 && (((uintptr_t)a->W | (uintptr_t)a->X) % 16) == 0);
     CadProfScope prof(8, stream);
     switch (a->K) {
-        case 32: return launch_wxT<1>(a, stream);
-        case 64: return launch_wxT<2>(a, stream);
-        case 128: return launch_wxT<4>(a, stream);
-        case 256: return launch_wxT<8>(a, stream);
-        case 512: return launch_wxT<16>(a, stream);
+        case 32: return launch_wxT<TE, 1>(a, stream);
+        case 64: return launch_wxT<TE, 2>(a, stream);
+        case 128: return launch_wxT<TE, 4>(a, stream);
+        case 256: return launch_wxT<TE, 8>(a, stream);
+        case 512: return launch_wxT<TE, 16>(a, stream);
         default: return CAD_ERR_UNSUPPORTED;
     }
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
+extern "C" int cad_proj_wxT(const cad_proj_args* a, void* stream) { return proj_wxT<bf16_t>(a, stream); }
+#endif
 
 
-template <int KS>
+template <typename TE, int KS>
 static int launch_wx(const cad_proj_args* a, void* stream) {
     typedef GxCfg<KS> C;
     const int64_t nblk = (a->T + C::NT - 1) / C::NT;
@@ -1055,36 +1075,41 @@ static int launch_wx(const cad_proj_args* a, void* stream) {
     if (gx > nblk) gx = nblk;
     dim3 grid((unsigned)gx, (unsigned)my), block(64 * GP_WAVES);
     if (a->acc) {
-        GP_BIG_LDS((proj_wx_kernel<KS, true>), C::LDS);
-        CAD_LAUNCH((proj_wx_kernel<KS, true>), grid, block, C::LDS, stream, *a);
+        GP_BIG_LDS((proj_wx_kernel<TE, KS, true>), C::LDS);
+        CAD_LAUNCH((proj_wx_kernel<TE, KS, true>), grid, block, C::LDS, stream, *a);
     } else {
-        GP_BIG_LDS((proj_wx_kernel<KS, false>), C::LDS);
-        CAD_LAUNCH((proj_wx_kernel<KS, false>), grid, block, C::LDS, stream, *a);
+        GP_BIG_LDS((proj_wx_kernel<TE, KS, false>), C::LDS);
+        CAD_LAUNCH((proj_wx_kernel<TE, KS, false>), grid, block, C::LDS, stream, *a);
     }
     return cad_after_launch();
 }
 
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_wx_supported(int K, int64_t T) { return K >= 8 && K <= 64 && (K % 8) == 0 && T >= 8 && (T % 8) == 0; }
+#endif
 // thin M / deep K variant (x_proj, d(dt_lr)): M <= 64 output rows, K a multiple of 64 up to 1024; the addend (may alias out) carries the
 // other K half of a product whose W does not fit LDS in one piece (x_proj at d_inner 1024: 64 rows x 1024)
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_wx_thin_supported(int M, int K, int64_t T) {
     return M >= 1 && M <= 64 && K > 64 && K <= 1024 && (K % 64) == 0 && T >= 8 && (T % 8) == 0 &&
            GtCfg::lds(M, K) <= 160 * 1024;
 }
+#endif
 
-template <int MB>
+template <typename TE, int MB>
 static int launch_wx_thin(const cad_proj_args* a, void* stream) {
     const int64_t nblk = (a->T + GtCfg::NT - 1) / GtCfg::NT;
     int64_t gx = cad_cu_count();  // one workgroup per CU
     if (gx > nblk) gx = nblk;
     const size_t lds = GtCfg::lds(MB * 16, a->K);
     dim3 grid((unsigned)gx), block(64 * GP_WAVES);
-    GP_BIG_LDS((proj_wx_thin_kernel<MB>), lds);
-    CAD_LAUNCH((proj_wx_thin_kernel<MB>), grid, block, lds, stream, *a);
+    GP_BIG_LDS((proj_wx_thin_kernel<TE, MB>), lds);
+    CAD_LAUNCH((proj_wx_thin_kernel<TE, MB>), grid, block, lds, stream, *a);
     return cad_after_launch();
 }
 
-extern "C" int cad_proj_wx(const cad_proj_args* a, void* stream) {
+template <typename TE>
+static int proj_wx(const cad_proj_args* a, void* stream) {
     CAD_CHECK_ARG(a && a->W && a->X && a->out && a->T > 0 && a->M > 0 && a->K > 0);
     if (a->act == 0 && cad_proj_wx_thin_supported(a->M, a->K, a->T)) {
         CAD_CHECK_ARG(a->ldw >= a->K && a->ldx >= a->T && a->ldo >= a->T);
@@ -1093,10 +1118,10 @@ extern "C" int cad_proj_wx(const cad_proj_args* a, void* stream) {
         CAD_CHECK_ARG(a->acc == nullptr || (a->ldacc >= a->T && (a->ldacc % 4) == 0 && ((uintptr_t)a->acc % 8) == 0));
         CadProfScope prof(8, stream);
         switch ((a->M + 15) / 16) {
-            case 1: return launch_wx_thin<1>(a, stream);
-            case 2: return launch_wx_thin<2>(a, stream);
-            case 3: return launch_wx_thin<3>(a, stream);
-            default: return launch_wx_thin<4>(a, stream);
+            case 1: return launch_wx_thin<TE, 1>(a, stream);
+            case 2: return launch_wx_thin<TE, 2>(a, stream);
+            case 3: return launch_wx_thin<TE, 3>(a, stream);
+            default: return launch_wx_thin<TE, 4>(a, stream);
         }
     }
     if (!cad_proj_wx_supported(a->K, a->T)) return CAD_ERR_UNSUPPORTED;
@@ -1105,8 +1130,11 @@ extern "C" int cad_proj_wx(const cad_proj_args* a, void* stream) {
     CAD_CHECK_ARG((a->ldw % 8) == 0 && (a->ldx % 8) == 0 && (a->ldo % 8) == 0 && (a->ldacc % 8) == 0);
     CAD_CHECK_ARG((((uintptr_t)a->W | (uintptr_t)a->X | (uintptr_t)a->out | (uintptr_t)a->acc) % 16) == 0);
     CadProfScope prof(8, stream);
-    return a->K <= 32 ? launch_wx<1>(a, stream) : launch_wx<2>(a, stream);
+    return a->K <= 32 ? launch_wx<TE, 1>(a, stream) : launch_wx<TE, 2>(a, stream);
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
+extern "C" int cad_proj_wx(const cad_proj_args* a, void* stream) { return proj_wx<bf16_t>(a, stream); }
+#endif
 
 static size_t gt_wgrad_lds(int M, int K, bool prod) {
     const int mb = (M + 15) / 16;
@@ -1114,11 +1142,14 @@ static size_t gt_wgrad_lds(int M, int K, bool prod) {
     const size_t exch = (size_t)4 * (K / GtCfg::KC) * mb * 1024;
     return lds < exch ? exch : lds;
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_wx_wgrad_supported(int M, int K, int64_t T) {
     return (M == 16 || M == 32) && (K == 256 || K == 512) && T >= GtCfg::NT && (T % GtCfg::NT) == 0 &&
            gt_wgrad_lds(M, K, true) <= 160 * 1024;
 }
+#endif
 // the weight gradient alone (cad_proj_args.W == NULL, out == NULL): any M <= 64
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_wgrad_only_supported(int M, int K, int64_t T) {
     return M >= 1 && M <= 64 && (K == 256 || K == 512) && T >= GtCfg::NT && (T % GtCfg::NT) == 0 &&
            gt_wgrad_lds(M, K, false) <= 160 * 1024;
@@ -1127,8 +1158,9 @@ extern "C" int cad_proj_wx_wgrad_partials(int64_t T) {
     const int64_t nblk = T / GtCfg::NT;
     return (int)(nblk < 256 ? (nblk < 1 ? 1 : nblk) : 256);
 }
+#endif
 
-template <int MB, int NCH, bool PROD>
+template <typename TE, int MB, int NCH, bool PROD>
 static int launch_wx_wgrad(const cad_proj_args* a, void* stream) {
     const int gx = cad_proj_wx_wgrad_partials(a->T);
     size_t lds = (PROD ? GtCfg::lds(MB * 16, NCH * GtCfg::KC) : (size_t)GtCfg::RING * GtCfg::XBUF) + 2 * (size_t)MB * 16 * GtCfg::XROW;
@@ -1136,12 +1168,13 @@ static int launch_wx_wgrad(const cad_proj_args* a, void* stream) {
     if (lds < exch) lds = exch;
     if (lds > 160 * 1024) return CAD_ERR_UNSUPPORTED;  // (the *_supported predicates exclude these shapes)
     dim3 grid((unsigned)gx), block(64 * GP_WAVES);
-    GP_BIG_LDS((proj_wx_thin_wgrad_kernel<MB, NCH, PROD>), lds);
-    CAD_LAUNCH((proj_wx_thin_wgrad_kernel<MB, NCH, PROD>), grid, block, lds, stream, *a);
+    GP_BIG_LDS((proj_wx_thin_wgrad_kernel<TE, MB, NCH, PROD>), lds);
+    CAD_LAUNCH((proj_wx_thin_wgrad_kernel<TE, MB, NCH, PROD>), grid, block, lds, stream, *a);
     return cad_after_launch();
 }
 
-extern "C" int cad_proj_wx_wgrad(const cad_proj_args* a, void* stream) {
+template <typename TE>
+static int proj_wx_wgrad(const cad_proj_args* a, void* stream) {
     CAD_CHECK_ARG(a && a->X && a->wg_y && a->wg_partials && a->acc == nullptr && a->act == 0);
     CAD_CHECK_ARG(a->ldx >= a->T && a->ld_wg_y >= a->T && (a->ldx % 8) == 0 && (a->ld_wg_y % 8) == 0);
     CAD_CHECK_ARG((((uintptr_t)a->X | (uintptr_t)a->wg_y) % 16) == 0);
@@ -1150,7 +1183,7 @@ extern "C" int cad_proj_wx_wgrad(const cad_proj_args* a, void* stream) {
         if (!cad_proj_wgrad_only_supported(a->M, a->K, a->T)) return CAD_ERR_UNSUPPORTED;
         const int mb = (a->M + 15) / 16;
 #define GW_ONLY(MB_)                                                                                     \
-    return a->K == 256 ? launch_wx_wgrad<MB_, 4, false>(a, stream) : launch_wx_wgrad<MB_, 8, false>(a, stream)
+    return a->K == 256 ? launch_wx_wgrad<TE, MB_, 4, false>(a, stream) : launch_wx_wgrad<TE, MB_, 8, false>(a, stream)
         switch (mb) {
             case 1: GW_ONLY(1);
             case 2: GW_ONLY(2);
@@ -1163,46 +1196,58 @@ extern "C" int cad_proj_wx_wgrad(const cad_proj_args* a, void* stream) {
     if (!cad_proj_wx_wgrad_supported(a->M, a->K, a->T)) return CAD_ERR_UNSUPPORTED;
     CAD_CHECK_ARG(a->ldw >= a->K && a->ldo >= a->T && (a->ldw % 8) == 0 && (a->ldo % 4) == 0);
     CAD_CHECK_ARG(((uintptr_t)a->W % 16) == 0 && ((uintptr_t)a->out % 8) == 0);
-    if (a->M == 16) return a->K == 256 ? launch_wx_wgrad<1, 4, true>(a, stream) : launch_wx_wgrad<1, 8, true>(a, stream);
-    return a->K == 256 ? launch_wx_wgrad<2, 4, true>(a, stream) : launch_wx_wgrad<2, 8, true>(a, stream);
+    if (a->M == 16) return a->K == 256 ? launch_wx_wgrad<TE, 1, 4, true>(a, stream) : launch_wx_wgrad<TE, 1, 8, true>(a, stream);
+    return a->K == 256 ? launch_wx_wgrad<TE, 2, 4, true>(a, stream) : launch_wx_wgrad<TE, 2, 8, true>(a, stream);
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
+extern "C" int cad_proj_wx_wgrad(const cad_proj_args* a, void* stream) { return proj_wx_wgrad<bf16_t>(a, stream); }
+#endif
 
 
 // ---- cad_proj_xTw ------------------------------------------------------------------------------------------------------------------
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_proj_xTw_supported(int M, int K, int64_t T) {
     return (M == 128 || M == 256) && (K == 256 || K == 512) && T >= 8 && (T % 8) == 0;
 }
+#endif
 
-template <int MB, int KS>
+template <typename TE, int MB, int KS>
 static int launch_xTw(const cad_proj_tm_args* a, void* stream) {
     const int64_t nblk = (a->T + GtCfg::NT - 1) / GtCfg::NT;
     int64_t gx = cad_cu_count();  // one workgroup per CU
     if (gx > nblk) gx = nblk;
     const size_t lds = (size_t)GP_XTW_RING * GtCfg::XBUF;
     dim3 grid((unsigned)gx), block(64 * GP_WAVES);
-    GP_BIG_LDS((proj_xTw_kernel<MB, KS>), lds);
-    CAD_LAUNCH((proj_xTw_kernel<MB, KS>), grid, block, lds, stream, *a);
+    GP_BIG_LDS((proj_xTw_kernel<TE, MB, KS>), lds);
+    CAD_LAUNCH((proj_xTw_kernel<TE, MB, KS>), grid, block, lds, stream, *a);
     return cad_after_launch();
 }
 
-extern "C" int cad_proj_xTw(const cad_proj_tm_args* a, void* stream) {
+template <typename TE>
+static int proj_xTw(const cad_proj_tm_args* a, void* stream) {
     CAD_CHECK_ARG(a && a->W && a->X && a->out && a->T > 0 && a->M > 0 && a->K > 0);
     if (!cad_proj_xTw_supported(a->M, a->K, a->T)) return CAD_ERR_UNSUPPORTED;
     CAD_CHECK_ARG(a->ldw >= a->K && a->ldx >= a->T && a->ldo >= a->M);
     CAD_CHECK_ARG((a->ldw % 8) == 0 && (a->ldx % 8) == 0 && (a->ldo % 4) == 0);
     CAD_CHECK_ARG((((uintptr_t)a->W | (uintptr_t)a->X | (uintptr_t)a->X2) % 16) == 0 && ((uintptr_t)a->out % 8) == 0);
     CadProfScope prof(8, stream);
-    if (a->M == 256) return a->K == 512 ? launch_xTw<2, 16>(a, stream) : launch_xTw<2, 8>(a, stream);
-    return a->K == 512 ? launch_xTw<1, 16>(a, stream) : launch_xTw<1, 8>(a, stream);
+    if (a->M == 256) return a->K == 512 ? launch_xTw<TE, 2, 16>(a, stream) : launch_xTw<TE, 2, 8>(a, stream);
+    return a->K == 512 ? launch_xTw<TE, 1, 16>(a, stream) : launch_xTw<TE, 1, 8>(a, stream);
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
+extern "C" int cad_proj_xTw(const cad_proj_tm_args* a, void* stream) { return proj_xTw<bf16_t>(a, stream); }
+#endif
 
 // ---- cad_gemm_stream ----------------------------------------------------------------------------------------------------------------
+#ifndef CAD_GEMM_TEMPLATES_ONLY
 extern "C" int cad_gemm_stream_supported(int64_t R, int64_t C, int64_t K, int nslices) {
     return R >= GsCfg::RT && (R % GsCfg::RT) == 0 && C >= GsCfg::CT && (C % GsCfg::CT) == 0 && nslices >= 1 && K > 0 &&
            (K % nslices) == 0 && ((K / nslices) % GsCfg::KC) == 0;
 }
+#endif
 
-extern "C" int cad_gemm_stream(const cad_gemm_stream_args* a, void* stream) {
+template <typename TE>
+static int gemm_stream(const cad_gemm_stream_args* a, void* stream) {
     CAD_CHECK_ARG(a && a->A && a->B && a->out && (a->mode == CAD_GEMM_PARTIALS || a->mode == CAD_GEMM_OUT_T_BF16));
     if (!cad_gemm_stream_supported(a->R, a->C, a->K, a->nslices)) return CAD_ERR_UNSUPPORTED;
     CAD_CHECK_ARG(a->lda >= a->K && a->ldb >= a->C && (a->lda % 8) == 0 && (a->ldb % 8) == 0);
@@ -1214,15 +1259,19 @@ extern "C" int cad_gemm_stream(const cad_gemm_stream_args* a, void* stream) {
     if (gx > nitems) gx = nitems;
     dim3 grid((unsigned)gx), block(64 * GP_WAVES);
     if (a->mode == CAD_GEMM_PARTIALS) {
-        GP_BIG_LDS((gemm_stream_kernel<CAD_GEMM_PARTIALS>), GsCfg::LDS);
-        CAD_LAUNCH((gemm_stream_kernel<CAD_GEMM_PARTIALS>), grid, block, GsCfg::LDS, stream, *a);
+        GP_BIG_LDS((gemm_stream_kernel<CAD_GEMM_PARTIALS, TE>), GsCfg::LDS);
+        CAD_LAUNCH((gemm_stream_kernel<CAD_GEMM_PARTIALS, TE>), grid, block, GsCfg::LDS, stream, *a);
     } else {
-        GP_BIG_LDS((gemm_stream_kernel<CAD_GEMM_OUT_T_BF16>), GsCfg::LDS);
-        CAD_LAUNCH((gemm_stream_kernel<CAD_GEMM_OUT_T_BF16>), grid, block, GsCfg::LDS, stream, *a);
+        GP_BIG_LDS((gemm_stream_kernel<CAD_GEMM_OUT_T_BF16, TE>), GsCfg::LDS);
+        CAD_LAUNCH((gemm_stream_kernel<CAD_GEMM_OUT_T_BF16, TE>), grid, block, GsCfg::LDS, stream, *a);
     }
     return cad_after_launch();
 }
+#ifndef CAD_GEMM_TEMPLATES_ONLY
+extern "C" int cad_gemm_stream(const cad_gemm_stream_args* a, void* stream) { return gemm_stream<bf16_t>(a, stream); }
+#endif
 
+#ifndef CAD_GEMM_TEMPLATES_ONLY  // (the fp32 fold: one definition, in this translation unit)
 // ---- cad_fold_f32_multi: the fp32 partial tiles of a layer's weight gradients, every sum in one launch --------------------------------
 namespace {
 struct FoldF32Jobs {
@@ -1278,3 +1327,4 @@ extern "C" int cad_fold_f32_multi(const cad_fold_f32_job* jobs, int njobs, void*
     CAD_LAUNCH(fold_f32_multi_kernel, grid, block, 0, stream, kj);
     return cad_after_launch();
 }
+#endif

@@ -134,8 +134,8 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_head_fwd_mfma_kernel(cad_lm_
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                o[2 * q] = cad_bits2f(r.w[q] << 16);
-                o[2 * q + 1] = cad_bits2f(r.w[q] & 0xffff0000u);
+                o[2 * q] = cad_lo2f<T>(r.w[q]);
+                o[2 * q + 1] = cad_hi2f<T>(r.w[q]);
             }
         } else {
 #pragma unroll
@@ -342,8 +342,8 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_head_bwd_mfma_kernel(cad_lm_
                     if constexpr (sizeof(T) == 2) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            hv[q * 8 + 2 * e] = cad_bits2f(rw.w[e] << 16);
-                            hv[q * 8 + 2 * e + 1] = cad_bits2f(rw.w[e] & 0xffff0000u);
+                            hv[q * 8 + 2 * e] = cad_lo2f<T>(rw.w[e]);
+                            hv[q * 8 + 2 * e + 1] = cad_hi2f<T>(rw.w[e]);
                         }
                     } else {
 #pragma unroll
@@ -438,7 +438,7 @@ extern "C" int cad_lm_head_fwd(const cad_lm_head_args* a, void* stream) {
     CAD_CHECK_ARG(!a->labels || (a->loss_sum && a->count));
     if (a->V > LM_VMAX) return CAD_ERR_UNSUPPORTED;
     CadProfScope prof(7, stream);
-    if (a->dtype != CAD_F32 && a->dtype != CAD_BF16) return CAD_ERR_UNSUPPORTED;
+    if (a->dtype != CAD_F32 && a->dtype != CAD_BF16 && a->dtype != CAD_F16) return CAD_ERR_UNSUPPORTED;
     const bool mfma = lm_head_mfma(a->D, a->dtype) && ((uintptr_t)a->hidden % 32) == 0;
     const int64_t nb = mfma ? lm_head_blocks_mfma(a->rows) : lm_head_blocks(a->rows);
     dim3 grid((unsigned)nb), block(64 * LM_WAVES);
@@ -446,6 +446,8 @@ extern "C" int cad_lm_head_fwd(const cad_lm_head_args* a, void* stream) {
     do {                                                                                          \
         if (a->dtype == CAD_F32)                                                                  \
             CAD_LAUNCH((lm_head_fwd_mfma_kernel<float, NJ_>), grid, block, 0, stream, *a);        \
+        else if (a->dtype == CAD_F16)                                                             \
+            CAD_LAUNCH((lm_head_fwd_mfma_kernel<f16_t, NJ_>), grid, block, 0, stream, *a);        \
         else                                                                                      \
             CAD_LAUNCH((lm_head_fwd_mfma_kernel<bf16_t, NJ_>), grid, block, 0, stream, *a);       \
     } while (0)
@@ -457,6 +459,8 @@ extern "C" int cad_lm_head_fwd(const cad_lm_head_args* a, void* stream) {
         CAD_LAUNCH((lm_head_fwd_mfma_kernel<bf16_t, 16>), grid, block, 0, stream, *a);
     else if (a->dtype == CAD_F32)
         CAD_LAUNCH((lm_head_fwd_kernel<float>), grid, block, 0, stream, *a);
+    else if (a->dtype == CAD_F16)
+        CAD_LAUNCH((lm_head_fwd_kernel<f16_t>), grid, block, 0, stream, *a);
     else
         CAD_LAUNCH((lm_head_fwd_kernel<bf16_t>), grid, block, 0, stream, *a);
 #undef LM_MFMA
@@ -480,7 +484,7 @@ extern "C" int cad_lm_head_bwd(const cad_lm_head_bwd_args* a, void* stream) {
     CAD_CHECK_ARG(a->n_strands == 1 || (a->n_strands == 2 && a->comp));
     CAD_CHECK_ARG(!a->labels || (a->logits && a->loss_scale));
     CAD_CHECK_ARG(a->labels || a->dlogits);
-    if (!cad_lm_head_bwd_supported(a->D, a->V) || (a->dtype != CAD_F32 && a->dtype != CAD_BF16)) return CAD_ERR_UNSUPPORTED;
+    if (!cad_lm_head_bwd_supported(a->D, a->V) || (a->dtype != CAD_F32 && a->dtype != CAD_BF16 && a->dtype != CAD_F16)) return CAD_ERR_UNSUPPORTED;
     CAD_CHECK_ARG(a->ld == 0 || (a->ld >= a->D && (a->ld % 8) == 0));
     CAD_CHECK_ARG((((uintptr_t)a->hidden | (uintptr_t)a->dhidden | (uintptr_t)a->dw_partials) % 16) == 0);
     CadProfScope prof(7, stream);
@@ -489,6 +493,8 @@ extern "C" int cad_lm_head_bwd(const cad_lm_head_bwd_args* a, void* stream) {
     do {                                                                                          \
         if (a->dtype == CAD_F32)                                                                  \
             CAD_LAUNCH((lm_head_bwd_mfma_kernel<float, NCB_>), grid, block, 0, stream, *a);       \
+        else if (a->dtype == CAD_F16)                                                             \
+            CAD_LAUNCH((lm_head_bwd_mfma_kernel<f16_t, NCB_>), grid, block, 0, stream, *a);       \
         else                                                                                      \
             CAD_LAUNCH((lm_head_bwd_mfma_kernel<bf16_t, NCB_>), grid, block, 0, stream, *a);      \
     } while (0)

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
     constexpr int TILE = SC_TILE(SC_S), ROW = SC_ROW(SC_S);
     const cad_scan_bwd_args& a = sets.s[blockIdx.z];
     float* acc = smem + 4 * TILE;
-    constexpr bool PACKED = SC_SLAB_PACKED && sizeof(T) == 2 && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;
+    constexpr bool PACKED = SC_SLAB_PACKED && cad_is_bf16<T>::value && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;  // (bf16 MFMA flush)
     uint32_t* accp = (uint32_t*)acc;
     static_assert(!PACKED || SC_S == 8, "packed slab: two 4-item blocks per lane");
     // item vectors of the next chunk travel global -> LDS by DMA one chunk ahead (16-byte vectors: bf16, 8 items)
@@ -182,8 +182,9 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
     const int64_t nchunks = (L + SC_CHUNK - 1) / SC_CHUNK;
     const float keep = act ? 1.f : 0.f;  // padding waves (E % SC_W != 0) contribute nothing
     const int64_t part_stride = (int64_t)N * SB * L;
-    T* dBg = (T*)a.dB + (int64_t)blockIdx.x * part_stride;  // this workgroup's partial-sum slot
-    T* dCg = (T*)a.dC + (int64_t)blockIdx.x * part_stride;
+    typedef typename cad_slot_of<T>::type TS;  // slot element type (fp16 activations: bf16 slots)
+    TS* dBg = (TS*)a.dB + (int64_t)blockIdx.x * part_stride;  // this workgroup's partial-sum slot
+    TS* dCg = (TS*)a.dC + (int64_t)blockIdx.x * part_stride;
     // concurrent fold (cad_fold_partials_stream on another stream, include/caduceus_hip.h): one arrival per (row, chunk) and workgroup,
     // published once every slot store of the chunk has left the CU
     int* pub = (!CO && a.fold_counters) ? a.fold_counters + sb * nchunks : nullptr;
@@ -686,7 +687,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 if (!(SC_WHATIF & 1) && g < 2 && n0 + g < N) {
                     const int64_t p = base + (int64_t)(jb * 16 + jl) * SC_S;
                     // row (state n0 + g) of this workgroup's slot: scalar base + one per-lane select (g is 0 or 1 here)
-                    T* grow = (ten ? dCg : dBg) + ((int64_t)n0 * SB + sb) * L + (g ? SB * L : (int64_t)0);
+                    TS* grow = (ten ? dCg : dBg) + ((int64_t)n0 * SB + sb) * L + (g ? SB * L : (int64_t)0);
                     if (VEC) {
                         if (p < L) {
                             u32x4 o;
@@ -733,7 +734,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 const int t = threadIdx.x;
                 const int ten = t / (2 * QT), s = (t / QT) & 1, idx = t % QT;
                 const float* tile = acc + (SC_SLAB_BUFS == 2 ? buf : 0) * ACC_BUF + ten * ACC_TILE;
-                T* grow = (ten ? dCg : dBg) + ((int64_t)(n0 + s) * SB + sb) * L;
+                TS* grow = (ten ? dCg : dBg) + ((int64_t)(n0 + s) * SB + sb) * L;
 #pragma unroll
                 for (int h4 = 0; h4 < FT; h4 += FV) {
                     const int tok = idx * FT + h4;
@@ -755,15 +756,15 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                                     float o[FV];
 #pragma unroll
                                     for (int q = 0; q < FV; ++q) o[q] = v[FV - 1 - q];
-                                    cad_cvt_store<T, FV>(grow + (L - p - FV), o);
+                                    cad_cvt_store<TS, FV>(grow + (L - p - FV), o);
                                 } else {
-                                    cad_cvt_store<T, FV>(grow + p, v);
+                                    cad_cvt_store<TS, FV>(grow + p, v);
                                 }
                             }
                         } else {
 #pragma unroll
                             for (int q = 0; q < FV; ++q)
-                                if (p + q < L) grow[cad_phys(p + q, L, rev)] = from_f32<T>(v[q]);
+                                if (p + q < L) grow[cad_phys(p + q, L, rev)] = from_f32<TS>(v[q]);
                         }
                     }
                 }
@@ -915,8 +916,10 @@ __device__ __forceinline__ void ld4p<bf16_t>(const bf16_t* p, float* o) {
     o[2] = cad_bits2f(t.w[1] << 16), o[3] = cad_bits2f(t.w[1] & 0xffff0000u);
 }
 
+// T = the destination's element type; the slots are in cad_slot_of<T> (bf16 for an fp16 destination)
 template <typename T>
-__global__ void reduce_partials_kernel(const T* src, int nparts, int64_t n, T* dst, int vec) {
+__global__ void reduce_partials_kernel(const typename cad_slot_of<T>::type* src, int nparts, int64_t n, T* dst, int vec) {
+    typedef typename cad_slot_of<T>::type TS;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
         // (the library's one summation order, include/caduceus_hip.h: groups of CAD_FOLD_GROUP consecutive slots, then the group sums)
@@ -926,7 +929,7 @@ __global__ void reduce_partials_kernel(const T* src, int nparts, int64_t n, T* d
                 float g[4] = {0.f, 0.f, 0.f, 0.f};
                 for (int k = k0; k < nparts && k < k0 + CAD_FOLD_GROUP; ++k) {
                     float x[4];
-                    ld4p<T>(src + (int64_t)k * n + i, x);
+                    ld4p<TS>(src + (int64_t)k * n + i, x);
                     g[0] += x[0], g[1] += x[1], g[2] += x[2], g[3] += x[3];
                 }
                 s[0] += g[0], s[1] += g[1], s[2] += g[2], s[3] += g[3];
@@ -953,7 +956,8 @@ struct ReduceJobs {
 };
 template <typename T>
 __global__ void reduce_partials_multi_kernel(ReduceJobs jobs, int nparts, int64_t n) {
-    const T* src = (const T*)jobs.src[blockIdx.y];
+    typedef typename cad_slot_of<T>::type TS;
+    const TS* src = (const TS*)jobs.src[blockIdx.y];
     T* dst = (T*)jobs.dst[blockIdx.y];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {  // (n % 4 == 0, 16-byte aligned: checked)
@@ -962,7 +966,7 @@ __global__ void reduce_partials_multi_kernel(ReduceJobs jobs, int nparts, int64_
             float g[4] = {0.f, 0.f, 0.f, 0.f};
             for (int k = k0; k < nparts && k < k0 + CAD_FOLD_GROUP; ++k) {
                 float x[4];
-                ld4p<T>(src + (int64_t)k * n + i, x);
+                ld4p<TS>(src + (int64_t)k * n + i, x);
                 g[0] += x[0], g[1] += x[1], g[2] += x[2], g[3] += x[3];
             }
             s[0] += g[0], s[1] += g[1], s[2] += g[2], s[3] += g[3];
@@ -1268,10 +1272,10 @@ extern "C" int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void
     constexpr bool kLeanBuild = SC_BWD_LEAN && (SC_BWD_UNROLL_NP != 0) && SC_BWD_PREFETCH && SC_SLAB_PACKED && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;
 #define SC_BWD_LAUNCH(T, V)                                                                  \
     do {                                                                                     \
-        if (kLeanBuild && SC_BWD_UNROLL_NP && !a->carry_only && V && sizeof(T) == 2 && pref && all_dt &&   \
+        if (kLeanBuild && SC_BWD_UNROLL_NP && !a->carry_only && V && cad_is_bf16<T>::value && pref && all_dt &&   \
             a->N == 2 * SC_BWD_UNROLL_NP) {                                                  \
-            SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && sizeof(T) == 2>), shmem);             \
-            CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && sizeof(T) == 2>), grid, block, shmem, stream, ks); \
+            SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && cad_is_bf16<T>::value>), shmem);             \
+            CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && cad_is_bf16<T>::value>), grid, block, shmem, stream, ks); \
         } else if (SC_BWD_UNROLL_NP && !a->carry_only && V && sizeof(T) == 2 && a->N == 2 * SC_BWD_UNROLL_NP) { \
             SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP>), shmem);             \
             CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP>), grid, block, shmem, stream, ks); \
@@ -1293,6 +1297,11 @@ extern "C" int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void
             SC_BWD_LAUNCH(bf16_t, true);
         else
             SC_BWD_LAUNCH(bf16_t, false);
+    } else if (a->dtype == CAD_F16) {  // the generic / unrolled kernels (the lean instantiation, packed slab and prefetch are bf16's)
+        if (vec)
+            SC_BWD_LAUNCH(f16_t, true);
+        else
+            SC_BWD_LAUNCH(f16_t, false);
     } else {
         return CAD_ERR_UNSUPPORTED;
     }
@@ -1329,6 +1338,8 @@ extern "C" int cad_scan_bwd_gate_fix(const cad_scan_bwd_args* sets, int nsets, v
             CAD_LAUNCH((scan_gate_fix_kernel<float>), grid, block, 0, stream, *a);
         else if (a->dtype == CAD_BF16)
             CAD_LAUNCH((scan_gate_fix_kernel<bf16_t>), grid, block, 0, stream, *a);
+        else if (a->dtype == CAD_F16)
+            CAD_LAUNCH((scan_gate_fix_kernel<f16_t>), grid, block, 0, stream, *a);
         else
             return CAD_ERR_UNSUPPORTED;
     }
@@ -1421,6 +1432,8 @@ extern "C" int cad_reduce_partials(const void* src, int n_partials, int64_t n, v
         CAD_LAUNCH((reduce_partials_kernel<float>), grid, block, 0, stream, (const float*)src, n_partials, n, (float*)dst, vec);
     else if (dst_dtype == CAD_BF16)
         CAD_LAUNCH((reduce_partials_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)src, n_partials, n, (bf16_t*)dst, vec);
+    else if (dst_dtype == CAD_F16)  // bf16 slots (the scan backward's fp16 mode)
+        CAD_LAUNCH((reduce_partials_kernel<f16_t>), grid, block, 0, stream, (const bf16_t*)src, n_partials, n, (f16_t*)dst, vec);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
@@ -1450,6 +1463,8 @@ extern "C" int cad_reduce_partials_multi(const cad_reduce_job* jobs, int njobs, 
         CAD_LAUNCH((reduce_partials_multi_kernel<float>), grid, block, 0, stream, kj, n_partials, n);
     else if (dst_dtype == CAD_BF16)
         CAD_LAUNCH((reduce_partials_multi_kernel<bf16_t>), grid, block, 0, stream, kj, n_partials, n);
+    else if (dst_dtype == CAD_F16)
+        CAD_LAUNCH((reduce_partials_multi_kernel<f16_t>), grid, block, 0, stream, kj, n_partials, n);
     else
         return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();

@@ -169,7 +169,7 @@ __device__ __forceinline__ void sc_load_raw(const T* row, int64_t p0, int64_t L,
 template <typename T, int S>
 __device__ __forceinline__ void sc_unpack(const ScVec<T, S>& raw, int rev, float* out) {
     if constexpr (sizeof(T) == 2 && S % 2 == 0) {
-        // bf16: work on the raw dwords -- logical item j is physical element S-1-j on a right-to-left row, i.e. the
+        // 16-bit elements: work on the raw dwords -- logical item j is physical element S-1-j on a right-to-left row, i.e. the
         // dword order is reversed and the halves of every dword swap: one select + one rotate per dword
         constexpr int NW = S / 2;
 #ifdef CAD_EMU
@@ -185,8 +185,8 @@ __device__ __forceinline__ void sc_unpack(const ScVec<T, S>& raw, int rev, float
 #pragma unroll
         for (int q = 0; q < NW; ++q) {
             const uint32_t x = sc_rot(sc_sel(w[q], w[NW - 1 - q], rmask), rot);
-            out[2 * q] = cad_bits2f(x << 16);
-            out[2 * q + 1] = cad_bits2f(x & 0xFFFF0000u);
+            out[2 * q] = cad_lo2f<T>(x);
+            out[2 * q + 1] = cad_hi2f<T>(x);
         }
     } else {
 #pragma unroll
@@ -202,13 +202,13 @@ __device__ __forceinline__ void sc_load(const T* row, int64_t p0, int64_t L, int
 template <typename T, int S, bool VEC>
 __device__ __forceinline__ void sc_store(T* row, int64_t p0, int64_t L, int rev, const float* v) {
     if constexpr (VEC && sizeof(T) == 2 && (S == 8 || S == 16)) {
-        // bf16: convert in logical order, then reverse on the packed dwords (see sc_unpack)
+        // 16-bit elements: convert in logical order, then reverse on the packed dwords (see sc_unpack)
         if (p0 < L) {
             const int64_t l0 = rev ? (L - p0 - S) : p0;
             constexpr int NW = S / 2;
             uint32_t pk[NW];
 #pragma unroll
-            for (int q = 0; q < NW; ++q) pk[q] = cad_pack_bf16x2(v[2 * q], v[2 * q + 1]);
+            for (int q = 0; q < NW; ++q) pk[q] = cad_pack2<T>(v[2 * q], v[2 * q + 1]);
             const uint64_t rmask = sc_rev_mask(rev);
             const uint32_t rot = rev ? 16u : 0u;
 #pragma unroll
@@ -256,8 +256,8 @@ __device__ __forceinline__ void sc_unpack_d(const ScVec<T, S>& raw, float* out) 
 #pragma unroll
         for (int q = 0; q < NW; ++q) {
             const uint32_t x = w[REV ? NW - 1 - q : q];
-            out[2 * q] = cad_bits2f(REV ? (x & 0xFFFF0000u) : (x << 16));
-            out[2 * q + 1] = cad_bits2f(REV ? (x << 16) : (x & 0xFFFF0000u));
+            out[2 * q] = REV ? cad_hi2f<T>(x) : cad_lo2f<T>(x);
+            out[2 * q + 1] = REV ? cad_lo2f<T>(x) : cad_hi2f<T>(x);
         }
     } else {
         sc_unpack<T, S>(raw, REV ? 1 : 0, out);
@@ -275,7 +275,7 @@ __device__ __forceinline__ void sc_store_d(T* row, int64_t p0, int64_t L, const 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int k = q + t;
-                    o[t] = REV ? cad_pack_bf16x2(v[S - 1 - 2 * k], v[S - 2 - 2 * k]) : cad_pack_bf16x2(v[2 * k], v[2 * k + 1]);
+                    o[t] = REV ? cad_pack2<T>(v[S - 1 - 2 * k], v[S - 2 - 2 * k]) : cad_pack2<T>(v[2 * k], v[2 * k + 1]);
                 }
                 *(u32x4*)(row + l0 + 2 * q) = o;
             }
@@ -298,7 +298,7 @@ __device__ __forceinline__ ScDirSel sc_dir_sel(int rev) {
 }
 template <typename T, int S>
 __device__ __forceinline__ void sc_unpack_p(const ScVec<T, S>& raw, int rev, ScDirSel sel, float* out) {
-    if constexpr (sizeof(T) == 2 && S % 2 == 0) {
+    if constexpr (cad_is_bf16<T>::value && S % 2 == 0) {  // (the widening by byte placement is a bf16 fact; fp16 takes sc_unpack)
         constexpr int NW = S / 2;
 #ifdef CAD_EMU
         struct W { uint32_t w[NW]; };
@@ -480,7 +480,8 @@ __device__ __forceinline__ void sc_stage_store(StageRegs<T, SC_SV(S)>& r, float*
                 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                 uint32_t x = a[REV ? NW - 1 - i : i], y = b[REV ? NW - 1 - i : i];
                 if constexpr (MASK) x &= m0, y &= m1;
-                const uint32_t lo0 = x << 16, lo1 = y << 16, hi0 = x & 0xFFFF0000u, hi1 = y & 0xFFFF0000u;
+                const uint32_t lo0 = cad_f2bits(cad_lo2f<T>(x)), lo1 = cad_f2bits(cad_lo2f<T>(y));  // (bf16: shifts / ANDs)
+                const uint32_t hi0 = cad_f2bits(cad_hi2f<T>(x)), hi1 = cad_f2bits(cad_hi2f<T>(y));
                 u4 q;
                 if constexpr (REV)
                     q[0] = hi0, q[1] = hi1, q[2] = lo0, q[3] = lo1;  // the later physical token comes first

@@ -343,7 +343,7 @@ extern "C" int cad_scan_fwd_multi(const cad_scan_args* sets, int nsets, void* st
     CadProfScope prof(0, stream);
     dim3 grid((unsigned)((a->E + SC_W - 1) / SC_W), (unsigned)a->SB, (unsigned)nsets), block(64 * SC_W);
     const size_t shmem = (size_t)SC_RING_FWD * 2 * SC_TILE(SC_S) * sizeof(float) +
-                         ((SC_FWD_DMA && vec && a->dtype == CAD_BF16 && SC_S == 16) ? PRE_BYTES : 0);
+                         ((SC_FWD_DMA && vec && (a->dtype == CAD_BF16 || a->dtype == CAD_F16) && SC_S == 16) ? PRE_BYTES : 0);
 #define SC_FWD_LAUNCH(T, V)                                                                  \
     do {                                                                                     \
         if (SC_FWD_UNROLL_NP && !a->map_only && V && sizeof(T) == 2 && a->N == 2 * SC_FWD_UNROLL_NP) { \
@@ -367,6 +367,11 @@ extern "C" int cad_scan_fwd_multi(const cad_scan_args* sets, int nsets, void* st
             SC_FWD_LAUNCH(bf16_t, true);
         else
             SC_FWD_LAUNCH(bf16_t, false);
+    } else if (a->dtype == CAD_F16) {
+        if (vec)
+            SC_FWD_LAUNCH(f16_t, true);
+        else
+            SC_FWD_LAUNCH(f16_t, false);
     } else {
         return CAD_ERR_UNSUPPORTED;
     }

@@ -12,7 +12,7 @@ duplicated in/out projections.  Here:
   * activations between GEMMs and scans are channel-major (E, S*B, L): the in_proj GEMM writes that layout directly
     (W @ X^T) and every scan/conv access is a contiguous run along L.
 
-On THIS (generic, per-op autograd) path the dense projections go through ops.mm (fp32: the own cad_gemm_f32; bf16: torch.mm / hipBLASLt); the production configuration (tied, "add") runs
+On THIS (generic, per-op autograd) path the dense projections go through ops.mm (fp32, and fp16 on its exact fp32 widening: the own cad_gemm_f32; bf16: torch.mm / hipBLASLt); the production configuration (tied, "add") runs
 mixer.BiMambaMixerFn instead, whose projections are the library's own MFMA kernels (csrc/gemm.hip) -- no library GEMM on that step.
 """
 from __future__ import annotations
@@ -65,8 +65,9 @@ def bimamba_tframe(hn: torch.Tensor, mamba_fwd, mamba_rev, strategy: Optional[st
 
     strand_swap=True is the RCPS case: rows of strand 1 run every parameter set in the opposite direction."""
     dev = hn.device.type
-    if torch.is_autocast_enabled(dev) and torch.get_autocast_dtype(dev) != hn.dtype:
-        # a float16 request is computed in fp32 (mamba.act_dtype_of): keep autocast from re-casting the GEMMs in here
+    if torch.is_autocast_enabled(dev) and (torch.get_autocast_dtype(dev) != hn.dtype or hn.dtype == torch.float16):
+        # a float16 request is computed in fp32 (mamba.act_dtype_of), or -- inside mamba.fp16_kernels() -- by the fp16 kernels with
+        # fp32-accumulated products: either way keep autocast from re-casting the GEMMs in here
         with torch.autocast(dev, enabled=False):
             return _bimamba_tframe(hn, mamba_fwd, mamba_rev, strategy, strand_swap)
     return _bimamba_tframe(hn, mamba_fwd, mamba_rev, strategy, strand_swap)

@@ -6,7 +6,9 @@ initialisation follow upstream so that state dicts are interchangeable.
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import threading
 from typing import Optional
 
 import torch
@@ -28,13 +30,36 @@ def requested_dtype(x: torch.Tensor) -> torch.dtype:
     return dt
 
 
+_fp16 = threading.local()
+
+
+def fp16_kernels_enabled() -> bool:
+    """True inside `fp16_kernels()` (this thread)."""
+    return bool(getattr(_fp16, "on", False))
+
+
+@contextlib.contextmanager
+def fp16_kernels(enabled: bool = True):
+    """Opt-in fp16 compute path (thread-local): while active, a float16 request -- fp16 autocast, or fp16 inputs without
+    autocast -- runs the float16 instantiations of the kernels (fp16 activations in HBM, fp32 arithmetic and accumulation inside
+    the kernels, fp32 parameters: the contract of the bf16 path) instead of the fp32 kernels.  `enabled=False` switches it off
+    for a nested region.  CaduceusConfig(fp16_kernels=True) enters it in the models' forward."""
+    prev = getattr(_fp16, "on", False)
+    _fp16.on = bool(enabled)
+    try:
+        yield
+    finally:
+        _fp16.on = prev
+
+
 def act_dtype_of(x: torch.Tensor) -> torch.dtype:
-    """Compute dtype of the kernels for input x.  fp32 and bf16 are implemented; a float16 request (the reference's own AMP
-    precision, and vep_embeddings.py:352) is COMPUTED BY THE FP32 KERNELS -- at least as accurate as fp16 arithmetic, no fp16
-    instantiations of the kernels -- and the module outputs are rounded to float16 (as_requested)."""
+    """Compute dtype of the kernels for input x.  fp32 and bf16 are implemented, and fp16 behind the opt-in `fp16_kernels()`.
+    Without the opt-in a float16 request (the reference's own AMP precision, and vep_embeddings.py:352) is COMPUTED BY THE FP32
+    KERNELS -- at least as accurate as fp16 arithmetic -- and the module outputs are rounded to float16 (as_requested); inside
+    `fp16_kernels()` it is computed by the fp16 kernels and this returns torch.float16."""
     dt = requested_dtype(x)
     if dt == torch.float16:
-        return torch.float32
+        return torch.float16 if fp16_kernels_enabled() else torch.float32
     if dt not in (torch.float32, torch.bfloat16):
         raise NotImplementedError(f"caduceus_amd computes in float32 or bfloat16 (requested {dt}); on MI355X use bf16")
     return dt

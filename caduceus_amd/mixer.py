@@ -93,8 +93,8 @@ def _kchunks(T: int) -> int:
 def _wgrad_cm_cm(a_cm: torch.Tensor, b_cm: torch.Tensor) -> torch.Tensor:
     """a (M, T) @ b (N, T)^T with both operands channel-major (T contiguous) -> (M, N) fp32."""
     M, T = a_cm.shape
-    if a_cm.dtype == torch.float32:  # the own fp32 matrix-core kernel cuts K itself (ops.mm_f32)
-        return ops.mm_f32(a_cm, b_cm.t())
+    if a_cm.dtype in (torch.float32, torch.float16):  # the own fp32 matrix-core kernel cuts K itself (ops.mm_f32; fp16: exact widening)
+        return ops.mm_f32(a_cm.float(), b_cm.float().t())
     n = _kchunks(T)
     if b_cm.shape[0] <= 16 and n >= 64 and T % 16 == 0:
         n = 16  # thin products (dW_dt): fewer, deeper chunks (tools/wgrad_sweep.py: 48 vs 55 us at T = 262144)
@@ -128,8 +128,8 @@ def _wgrad_cm_tm(a_cm: torch.Tensor, b_tm: torch.Tensor) -> torch.Tensor:
         own = ops.wgrad_cm_tm(a_cm, b_tm)
         if own is not None:
             return own
-    if a_cm.dtype == torch.float32:
-        return ops.mm_f32(a_cm, b_tm)
+    if a_cm.dtype in (torch.float32, torch.float16):
+        return ops.mm_f32(a_cm.float(), b_tm.float())
     n = _kchunks(T)
     if n == 1:
         return ops.mm(a_cm, b_tm).float()
@@ -454,7 +454,7 @@ class BiMambaMixerFn(torch.autograd.Function):
             dz_r = dz if i == 1 else None
             dA, dD, dbias = zbuf[5 * i:5 * i + 3]
             npart = lib.cad_scan_bwd_partials(E)
-            dBC = torch.empty((2, npart, N, SB, Lq), dtype=act, device=xc.device)
+            dBC = torch.empty((2, npart, N, SB, Lq), dtype=ops.scan_slot_dtype(act), device=xc.device)
             Bm, Cm = dbc[R:R + N], dbc[R + N:]
             stream = L.stream_and_check(xc, delta, A, Bm, Cm, Df, z, bfz, dy, state, du, ddelta, dz, dA, dBC, dD, dbias)
             args[i] = L.ScanBwdArgs(L.ptr(xc), L.ptr(delta), L.ptr(A), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z),
@@ -536,6 +536,8 @@ class BiMambaMixerFn(torch.autograd.Function):
             else:
                 if du.dtype == torch.float32:
                     ops.mm_f32(w_x.t(), ddbc.view(R + 2 * N, T), out=du.view(E, T), addend=du.view(E, T))
+                elif du.dtype == torch.float16:  # (shapes the fp16 MFMA kernel does not serve: the fp32 kernel on the exact widening)
+                    du.view(E, T).copy_(ops.mm_f32(w_x.t().float(), ddbc.view(R + 2 * N, T).float(), addend=du.view(E, T).float()))
                 else:
                     du.view(E, T).addmm_(w_x.t(), ddbc.view(R + 2 * N, T))
             dxcs.append(du)

@@ -5,6 +5,7 @@ Same public classes, constructor / forward signatures, module tree and state-dic
 path and reference checkpoints work unchanged; all arithmetic runs in the flip-free t-frame on the HIP kernels
 (caduceus_amd.engine / caduceus_amd.ops).  No dependency on mamba_ssm / causal_conv1d / triton.
 """
+import contextlib
 import math
 from functools import partial
 from typing import Optional, Tuple, Union
@@ -18,7 +19,7 @@ from transformers.modeling_outputs import BaseModelOutputWithNoAttention, Masked
 from . import engine, ops
 from . import mixer as mixer_sched
 from .configuration_caduceus import CaduceusConfig
-from .mamba import Block, Mamba, RMSNorm, act_dtype_of, as_requested, norm_params
+from .mamba import Block, Mamba, RMSNorm, act_dtype_of, as_requested, fp16_kernels, norm_params
 from .modeling_rcps import RCPSAddNormWrapper, RCPSEmbedding, RCPSLMHead, RCPSMambaBlock, RCPSWrapper
 
 
@@ -198,6 +199,11 @@ class CaduceusPreTrainedModel(PreTrainedModel):
     """modeling_caduceus.py:297-341."""
     config_class = CaduceusConfig
     base_model_prefix = "caduceus"
+
+    def _precision_scope(self):
+        """CaduceusConfig(fp16_kernels=True): the forward runs inside mamba.fp16_kernels() (a float16 request takes the fp16 kernels);
+        otherwise a no-op, which leaves an enclosing fp16_kernels() context in force."""
+        return fp16_kernels(True) if getattr(self.config, "fp16_kernels", False) else contextlib.nullcontext()
     supports_gradient_checkpointing = False
     _no_split_modules = ["BiMambaWrapper"]
 
@@ -266,18 +272,19 @@ class Caduceus(CaduceusPreTrainedModel):
     def forward(self, input_ids: torch.LongTensor = None, inputs_embeds: Optional[torch.FloatTensor] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None,
                 ) -> Union[torch.Tensor, Tuple, BaseModelOutputWithNoAttention]:
-        output_hidden_states = (output_hidden_states if output_hidden_states is not None
-                                else self.config.output_hidden_states)
-        return_dict = return_dict if return_dict is not None else self._return_dict_default
-        hidden_states, all_hidden_states = self.backbone(input_ids, inputs_embeds=inputs_embeds,
-                                                         output_hidden_states=output_hidden_states)
-        if return_dict:
-            return BaseModelOutputWithNoAttention(last_hidden_state=hidden_states,
-                                                  hidden_states=all_hidden_states if output_hidden_states else None)
-        elif output_hidden_states:
-            return hidden_states, all_hidden_states
-        else:
-            return hidden_states
+        with self._precision_scope():
+            output_hidden_states = (output_hidden_states if output_hidden_states is not None
+                                    else self.config.output_hidden_states)
+            return_dict = return_dict if return_dict is not None else self._return_dict_default
+            hidden_states, all_hidden_states = self.backbone(input_ids, inputs_embeds=inputs_embeds,
+                                                             output_hidden_states=output_hidden_states)
+            if return_dict:
+                return BaseModelOutputWithNoAttention(last_hidden_state=hidden_states,
+                                                      hidden_states=all_hidden_states if output_hidden_states else None)
+            elif output_hidden_states:
+                return hidden_states, all_hidden_states
+            else:
+                return hidden_states
 
 
 class CaduceusForMaskedLM(CaduceusPreTrainedModel):
@@ -330,35 +337,36 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
                 labels: Optional[torch.LongTensor] = None, loss_weights: Optional[torch.FloatTensor] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None,
                 ) -> Union[Tuple, MaskedLMOutput]:
-        output_hidden_states = (output_hidden_states if output_hidden_states is not None
-                                else self.config.output_hidden_states)
-        return_dict = return_dict if return_dict is not None else self._return_dict_default
-        backbone = self.caduceus.backbone
-        collect = [] if output_hidden_states else None
-        hidden_t = backbone.forward_tframe(input_ids, inputs_embeds, collect)  # (S, B, L, D), never leaves the t-frame
-        ignore_index = getattr(self.config, "pad_token_id", None)
-        ignore_index = -100 if ignore_index is None else ignore_index
-        fused_loss = labels is not None and loss_weights is None
-        if self.config.rcps:
-            logits, loss = self.lm_head.forward_tframe(hidden_t, labels if fused_loss else None, ignore_index)
-        else:
-            w = self.lm_head.weight
-            if w.shape[0] <= 16 and getattr(self.lm_head, "bias", None) is None:
-                logits, loss = ops.lm_head(hidden_t, w, None, labels if fused_loss else None, ignore_index)
+        with self._precision_scope():
+            output_hidden_states = (output_hidden_states if output_hidden_states is not None
+                                    else self.config.output_hidden_states)
+            return_dict = return_dict if return_dict is not None else self._return_dict_default
+            backbone = self.caduceus.backbone
+            collect = [] if output_hidden_states else None
+            hidden_t = backbone.forward_tframe(input_ids, inputs_embeds, collect)  # (S, B, L, D), never leaves the t-frame
+            ignore_index = getattr(self.config, "pad_token_id", None)
+            ignore_index = -100 if ignore_index is None else ignore_index
+            fused_loss = labels is not None and loss_weights is None
+            if self.config.rcps:
+                logits, loss = self.lm_head.forward_tframe(hidden_t, labels if fused_loss else None, ignore_index)
             else:
-                h0 = hidden_t[0]
-                logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t()).view(*h0.shape[:-1], w.shape[0])
-                if self.lm_head.bias is not None:
-                    logits = logits + self.lm_head.bias.to(logits.dtype)
-                logits = logits.float()
-                loss = cross_entropy(logits, labels, ignore_index=ignore_index) if fused_loss else None
-        if labels is not None and loss_weights is not None:
-            loss = weighted_cross_entropy(logits, labels, loss_weights, ignore_index=ignore_index)
-        all_hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None
-        if not return_dict:
-            output = (logits,) + ((all_hidden,) if output_hidden_states else ())
-            return (loss,) + output if loss is not None else output
-        return MaskedLMOutput(loss=loss, logits=logits, hidden_states=all_hidden)
+                w = self.lm_head.weight
+                if w.shape[0] <= 16 and getattr(self.lm_head, "bias", None) is None:
+                    logits, loss = ops.lm_head(hidden_t, w, None, labels if fused_loss else None, ignore_index)
+                else:
+                    h0 = hidden_t[0]
+                    logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t()).view(*h0.shape[:-1], w.shape[0])
+                    if self.lm_head.bias is not None:
+                        logits = logits + self.lm_head.bias.to(logits.dtype)
+                    logits = logits.float()
+                    loss = cross_entropy(logits, labels, ignore_index=ignore_index) if fused_loss else None
+            if labels is not None and loss_weights is not None:
+                loss = weighted_cross_entropy(logits, labels, loss_weights, ignore_index=ignore_index)
+            all_hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None
+            if not return_dict:
+                output = (logits,) + ((all_hidden,) if output_hidden_states else ())
+                return (loss,) + output if loss is not None else output
+            return MaskedLMOutput(loss=loss, logits=logits, hidden_states=all_hidden)
 
 
 class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
@@ -433,33 +441,34 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
     def forward(self, input_ids: torch.LongTensor = None, inputs_embeds: Optional[torch.FloatTensor] = None,
                 labels: Optional[torch.LongTensor] = None, output_hidden_states: Optional[bool] = None,
                 return_dict: Optional[bool] = None) -> Union[Tuple, SequenceClassifierOutput]:
-        return_dict = return_dict if return_dict is not None else self._return_dict_default
-        backbone = self.caduceus.backbone
-        collect = [] if output_hidden_states else None
-        conjoin = (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
-        if conjoin:
-            if input_ids is None:
-                raise AssertionError("`input_ids` must be provided for conjoining.")
-            if input_ids.ndim != 3:
-                raise AssertionError("`input_ids` must be 3D tensor: channels corresponds to forward and rc strands.")
-            B = input_ids.shape[0]
-            both = torch.cat([input_ids[..., 0], input_ids[..., 1]], dim=0)  # one pass over (2B, L)
-            t = backbone.forward_tframe(both, None, collect)[0]               # (2B, L, D)
-            pooled = [self.pool_hidden_states(t[:B]), self.pool_hidden_states(t[B:])]
-            if collect is not None:  # the reference reports the hidden states of its first (forward-strand) pass
-                collect = [h[:, :B] for h in collect]
-        else:
-            t = backbone.forward_tframe(input_ids, inputs_embeds if self.config.rcps else None, collect)
-            pooled = [self.pool_hidden_states(t[0])]
-            if self.config.rcps:  # second strand: positions run the other way in the reference's stacked frame
-                pooled.append(self.pool_hidden_states(t[1], reversed_positions=True))
-        wdt = self.score.weight.dtype
-        logits = self.score(pooled[0].to(wdt))
-        if len(pooled) == 2:
-            logits = (logits + self.score(pooled[1].to(wdt))) / 2
-        loss = self._sequence_loss(logits, labels) if labels is not None else None
-        hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None
-        if not return_dict:
-            out = (logits,) + ((hidden,) if hidden is not None else ())
-            return ((loss,) + out) if loss is not None else out
-        return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=hidden)
+        with self._precision_scope():
+            return_dict = return_dict if return_dict is not None else self._return_dict_default
+            backbone = self.caduceus.backbone
+            collect = [] if output_hidden_states else None
+            conjoin = (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
+            if conjoin:
+                if input_ids is None:
+                    raise AssertionError("`input_ids` must be provided for conjoining.")
+                if input_ids.ndim != 3:
+                    raise AssertionError("`input_ids` must be 3D tensor: channels corresponds to forward and rc strands.")
+                B = input_ids.shape[0]
+                both = torch.cat([input_ids[..., 0], input_ids[..., 1]], dim=0)  # one pass over (2B, L)
+                t = backbone.forward_tframe(both, None, collect)[0]               # (2B, L, D)
+                pooled = [self.pool_hidden_states(t[:B]), self.pool_hidden_states(t[B:])]
+                if collect is not None:  # the reference reports the hidden states of its first (forward-strand) pass
+                    collect = [h[:, :B] for h in collect]
+            else:
+                t = backbone.forward_tframe(input_ids, inputs_embeds if self.config.rcps else None, collect)
+                pooled = [self.pool_hidden_states(t[0])]
+                if self.config.rcps:  # second strand: positions run the other way in the reference's stacked frame
+                    pooled.append(self.pool_hidden_states(t[1], reversed_positions=True))
+            wdt = self.score.weight.dtype
+            logits = self.score(pooled[0].to(wdt))
+            if len(pooled) == 2:
+                logits = (logits + self.score(pooled[1].to(wdt))) / 2
+            loss = self._sequence_loss(logits, labels) if labels is not None else None
+            hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None
+            if not return_dict:
+                out = (logits,) + ((hidden,) if hidden is not None else ())
+                return ((loss,) + out) if loss is not None else out
+            return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=hidden)

@@ -466,8 +466,8 @@ class _ScanMulti(torch.autograd.Function):
             du, ddelta = torch.empty_like(u), torch.empty_like(u)
             dz = None if z is None else torch.empty_like(u)
             dA, dD, dbias = torch.zeros_like(Af), torch.zeros_like(Df), torch.zeros_like(bf)
-            npart = lib.cad_scan_bwd_partials(E)  # one fp32 partial-sum slot per workgroup (written, not accumulated)
-            dBC = torch.empty((2, npart, N, SB, Lq), dtype=u.dtype, device=u.device)
+            npart = lib.cad_scan_bwd_partials(E)  # one partial-sum slot per workgroup (written, not accumulated)
+            dBC = torch.empty((2, npart, N, SB, Lq), dtype=scan_slot_dtype(u.dtype), device=u.device)
             stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, dout, state, du, ddelta, dz, dA, dBC, dD, dbias)
             rl, rh = dirs[i]
             fix_list, fix_cnt = gate_fix_buffers(lib, u, N) if z is not None else (None, None)
@@ -556,7 +556,7 @@ class _ScanStateful(torch.autograd.Function):
         dz = None if z is None else torch.empty_like(u)
         dA, dD, dbias = torch.zeros_like(Af), torch.zeros_like(Df), torch.zeros_like(bf)
         npart = lib.cad_scan_bwd_partials(E)
-        dBC = torch.empty((2, npart, N, SB, Lq), dtype=u.dtype, device=u.device)
+        dBC = torch.empty((2, npart, N, SB, Lq), dtype=scan_slot_dtype(u.dtype), device=u.device)
         dh0 = torch.empty((E, SB, N), dtype=torch.float32, device=u.device)
         stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, dout, state, du, ddelta, dz, dA, dBC, dD, dbias, dhT, dh0)
         fix_list, fix_cnt = gate_fix_buffers(lib, u, N) if z is not None else (None, None)
@@ -623,7 +623,7 @@ class _LmHead(torch.autograd.Function):
         # channel block of the kernel: the whole row (d_model 128 / 256) or 256 channels of a wider head (d_model 512: two launches,
         # the channels are independent in both products)
         DB = D if lib.cad_lm_head_bwd_supported(int(D), int(V)) else (256 if D % 256 == 0 and lib.cad_lm_head_bwd_supported(256, int(V)) else 0)
-        if (use_loss or dlogits is not None) and hidden.dtype in (torch.float32, torch.bfloat16) and DB and \
+        if (use_loss or dlogits is not None) and hidden.dtype in (torch.float32, torch.bfloat16, torch.float16) and DB and \
                 hidden.data_ptr() % 16 == 0:  # (kernel: 16-byte vector accesses)
             # on the matrix cores: softmax gradient, d hidden of both strands, dW partial slots (cad_lm_head_bwd)
             rows = hidden.numel() // (S * D)
@@ -794,54 +794,109 @@ def _own_f32(*ts) -> bool:
     return all(t.dtype == torch.float32 for t in ts)
 
 
+def _f16(*ts) -> bool:
+    return all(t.dtype == torch.float16 for t in ts)
+
+
+class _MmF16(torch.autograd.Function):
+    """a @ b (+ addend) of fp16 operands on cad_gemm_f32: exact widening, fp32 accumulation, ONE rounding of the fp16 result --
+    the fp16 products that no fp16 MFMA kernel serves (small / ragged shapes, the generic engine).  Gradients the same way."""
+
+    @staticmethod
+    def forward(ctx, a, b, addend):
+        ctx.save_for_backward(a, b)
+        return mm_f32(a.float(), b.float(), addend=None if addend is None else addend.float()).to(torch.float16)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        g32 = g.float()
+        da = mm_f32(g32, b.float().t()).to(a.dtype) if ctx.needs_input_grad[0] else None
+        db = mm_f32(a.float().t(), g32).to(b.dtype) if ctx.needs_input_grad[1] else None
+        return da, db, (g if ctx.needs_input_grad[2] else None)
+
+
 def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """torch.mm for the call sites that have no dedicated kernel: fp32 operands take the own fp32 matrix-core kernel (cad_gemm_f32;
-    differentiable), anything else (bf16 shapes the MFMA projection kernels do not serve) the library."""
+    differentiable), fp16 operands the same kernel on their exact fp32 widening (fp16 result), bf16 shapes the MFMA projection kernels
+    do not serve the library."""
     if _own_f32(a, b):
         if out is not None:
             return mm_f32(a, b, out=out)
         return _MmF32.apply(a, b, None)
+    if _f16(a, b):
+        if out is not None:
+            return out.copy_(mm_f32(a.float(), b.float()))
+        return _MmF16.apply(a, b, None)
     return torch.mm(a, b) if out is None else torch.mm(a, b, out=out)
 
 
 def addmm(acc: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """acc + a @ b (torch.addmm), fp32 on the own kernel."""
+    """acc + a @ b (torch.addmm), fp32 / fp16 on the own kernel."""
     if _own_f32(acc, a, b):
         return _MmF32.apply(a, b, acc)
+    if _f16(acc, a, b):
+        return _MmF16.apply(a, b, acc)
     return torch.addmm(acc, a, b)
 
 
 def bmm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """torch.bmm (no autograd use in this package), fp32 on the own kernel."""
+    """torch.bmm (no autograd use in this package), fp32 on the own kernel; fp16 operands: the same kernel on their fp32 widening,
+    fp32 result (the callers sum the batch in fp32)."""
     if _own_f32(a, b):
         return bmm_f32(a, b)
+    if _f16(a, b):
+        return bmm_f32(a.float(), b.float())
     return torch.bmm(a, b)
 
 
+# 16-bit element types of the MFMA projection kernels (csrc/gemm.hip): each cad_proj_* / cad_gemm_stream entry point has an fp16 sibling
+_MFMA_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def _proj_fn(name: str, dtype: torch.dtype):
+    """The bf16 entry point `name` or its fp16 sibling `name`_f16 (same argument struct)."""
+    return getattr(L.get_lib(), name + "_f16" if dtype == torch.float16 else name)
+
+
+def scan_slot_dtype(act: torch.dtype) -> torch.dtype:
+    """Element type of the scan backward's dB / dC partial slots: the activation dtype, except bf16 slots for fp16 activations (sums of
+    loss-scaled gradients keep fp32's range; include/caduceus_hip.h, cad_scan_bwd)."""
+    return torch.bfloat16 if act == torch.float16 else act
+
+
 def proj_supported(t: torch.Tensor, K: int) -> bool:
-    """The MFMA projection kernels take bf16 operands with a supported reduction length.  (K = 512, d_model 512: stand-alone and cold the
+    """The MFMA projection kernels take bf16 / fp16 operands with a supported reduction length.  (K = 512, d_model 512: stand-alone and cold the
     library GEMM is 18-25 % faster than the W-stationary kernel, inside the training step it is not -- 558.9 vs 555.9 ms per step;
     profiles/r04_proj_d512.txt.  The own kernel stays.)"""
-    return t.dtype == torch.bfloat16 and bool(L.get_lib().cad_proj_supported(int(K)))
+    return t.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_supported(int(K)))
 
 
 def proj_wxT(W: torch.Tensor, X: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out (M, T) channel-major = W (M, K) @ X (T, K)^T, bf16 in / fp32 accumulate / bf16 out (cad_proj_wxT)."""
+    """out (M, T) channel-major = W (M, K) @ X (T, K)^T, bf16 (fp16) in / fp32 accumulate / bf16 (fp16) out (cad_proj_wxT[_f16])."""
     M, K = W.shape
     T = X.shape[0]
     if X.shape[1] != K or W.stride(1) != 1 or X.stride(1) != 1:
         raise ValueError("proj_wxT: W (M, K) and X (T, K) with unit inner stride")
+    _same_mfma_dtype(W, X, out)
     if out is None:
-        out = torch.empty((M, T), dtype=torch.bfloat16, device=X.device)
+        out = torch.empty((M, T), dtype=X.dtype, device=X.device)
     stream = L.stream_and_check(W, X, out, contiguous=False)
     a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0), None, 0)
-    L.check(L.get_lib().cad_proj_wxT(C.byref(a), stream), "cad_proj_wxT")
+    L.check(_proj_fn("cad_proj_wxT", X.dtype)(C.byref(a), stream), "cad_proj_wxT")
     return out
+
+
+def _same_mfma_dtype(*ts) -> None:
+    """The 16-bit MFMA kernels read every operand in ONE element type (bf16 or fp16): a mixed call would reinterpret bits."""
+    dts = {t.dtype for t in ts if t is not None}
+    if len(dts) != 1 or not dts <= set(_MFMA_DTYPES):
+        raise TypeError(f"caduceus_amd projection kernels take bf16 or fp16 operands of one dtype, got {sorted(map(str, dts))}")
 
 
 def proj_wx_supported(t: torch.Tensor, K: int, T: int, M: Optional[int] = None) -> bool:
     """thin K (K <= 64, any M, optional addend), or -- when M is given -- thin M / deep K (M <= 64, K % 64 == 0, no addend)"""
-    if t.dtype != torch.bfloat16:
+    if t.dtype not in _MFMA_DTYPES:
         return False
     lib = L.get_lib()
     if lib.cad_proj_wx_supported(int(K), int(T)):
@@ -857,15 +912,16 @@ def proj_wx(W: torch.Tensor, X: torch.Tensor, out: Optional[torch.Tensor] = None
     T = X.shape[1]
     if X.shape[0] != K or W.stride(1) != 1 or X.stride(1) != 1:
         raise ValueError("proj_wx: W (M, K) and X (K, T) with unit inner stride")
+    _same_mfma_dtype(W, X, out, acc)
     if out is None:
-        out = torch.empty((M, T), dtype=torch.bfloat16, device=X.device)
+        out = torch.empty((M, T), dtype=X.dtype, device=X.device)
     stream = L.stream_and_check(W, X, out, acc, softplus_bias, contiguous=False)
     if softplus_bias is not None and (softplus_bias.dtype != torch.float32 or softplus_bias.numel() != M or
                                       not softplus_bias.is_contiguous()):
         raise ValueError("proj_wx: softplus_bias must be a contiguous fp32 vector of M elements")
     a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0), L.ptr(acc),
                    0 if acc is None else acc.stride(0), L.ptr(softplus_bias), 0 if softplus_bias is None else 1)
-    L.check(L.get_lib().cad_proj_wx(C.byref(a), stream), "cad_proj_wx")
+    L.check(_proj_fn("cad_proj_wx", X.dtype)(C.byref(a), stream), "cad_proj_wx")
     return out
 
 
@@ -877,7 +933,7 @@ FP8_MAX = 448.0
 
 
 def proj_xTw_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
-    return X.dtype == torch.bfloat16 and bool(L.get_lib().cad_proj_xTw_supported(int(M), int(K), int(T)))
+    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_xTw_supported(int(M), int(K), int(T)))
 
 
 def proj_xTw(W: torch.Tensor, X: torch.Tensor, X2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -885,12 +941,13 @@ def proj_xTw(W: torch.Tensor, X: torch.Tensor, X2: Optional[torch.Tensor] = None
     sum of the two directions' scan outputs through ONE set of resident weight fragments, fp32 accumulation over both panels."""
     M, K = W.shape
     T = X.shape[1]
+    _same_mfma_dtype(W, X, X2, out)
     if out is None:
         out = torch.empty((T, M), dtype=X.dtype, device=X.device)
     stream = L.stream_and_check(W, X, X2, out, contiguous=False)
     assert W.stride(1) == 1 and X.stride(1) == 1 and out.stride(1) == 1 and (X2 is None or (X2.stride() == X.stride() and X2.shape == X.shape))
     a = L.ProjTmArgs(L.ptr(W), L.ptr(X), L.ptr(X2), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0))
-    L.check(L.get_lib().cad_proj_xTw(C.byref(a), stream), "cad_proj_xTw")
+    L.check(_proj_fn("cad_proj_xTw", X.dtype)(C.byref(a), stream), "cad_proj_xTw")
     return out
 
 
@@ -927,7 +984,7 @@ def wgrad_cm_tm(a_cm: torch.Tensor, b_tm: torch.Tensor, return_partials: bool = 
     return_partials: the (slices, M, N) partial tiles as they are (the caller folds them, e.g. with fold_f32 next to other sums)."""
     M, T = a_cm.shape
     N = b_tm.shape[1]
-    if a_cm.dtype != torch.bfloat16 or b_tm.dtype != torch.bfloat16 or a_cm.stride(1) != 1 or b_tm.stride(1) != 1:
+    if a_cm.dtype not in _MFMA_DTYPES or b_tm.dtype != a_cm.dtype or a_cm.stride(1) != 1 or b_tm.stride(1) != 1:
         return None
     if a_cm.stride(0) % 8 or b_tm.stride(0) % 8 or a_cm.data_ptr() % 16 or b_tm.data_ptr() % 16:
         return None
@@ -937,7 +994,7 @@ def wgrad_cm_tm(a_cm: torch.Tensor, b_tm: torch.Tensor, return_partials: bool = 
     part = torch.empty((n, M, N), dtype=torch.float32, device=a_cm.device)
     stream = L.stream_and_check(a_cm, b_tm, part, contiguous=False)
     a = L.GemmStreamArgs(L.ptr(a_cm), L.ptr(b_tm), L.ptr(part), M, N, T, a_cm.stride(0), b_tm.stride(0), 0, n, GEMM_PARTIALS)
-    L.check(L.get_lib().cad_gemm_stream(C.byref(a), stream), "cad_gemm_stream")
+    L.check(_proj_fn("cad_gemm_stream", a_cm.dtype)(C.byref(a), stream), "cad_gemm_stream")
     if return_partials:
         return part
     return part[0] if n == 1 else part.sum(0)
@@ -957,17 +1014,17 @@ def proj_xTw_stream(Wt: torch.Tensor, X: torch.Tensor, col_fastest: bool = False
     shape is not served."""
     M, K = Wt.shape
     T = X.shape[1]
-    if Wt.dtype != torch.bfloat16 or X.dtype != torch.bfloat16 or Wt.stride(1) != 1 or X.stride(1) != 1:
+    if X.dtype not in _MFMA_DTYPES or Wt.dtype != X.dtype or Wt.stride(1) != 1 or X.stride(1) != 1:
         return None
     if Wt.stride(0) % 8 or X.stride(0) % 8 or Wt.data_ptr() % 16 or X.data_ptr() % 16:
         return None
     if not L.get_lib().cad_gemm_stream_supported(M, T, K, 1):
         return None
-    out = torch.empty((T, M), dtype=torch.bfloat16, device=X.device)
+    out = torch.empty((T, M), dtype=X.dtype, device=X.device)
     stream = L.stream_and_check(Wt, X, out, contiguous=False)
     a = L.GemmStreamArgs(L.ptr(Wt), L.ptr(X), L.ptr(out), M, T, K, Wt.stride(0), X.stride(0), out.stride(0), 1, GEMM_OUT_T_BF16,
                          int(bool(col_fastest)))
-    L.check(L.get_lib().cad_gemm_stream(C.byref(a), stream), "cad_gemm_stream")
+    L.check(_proj_fn("cad_gemm_stream", X.dtype)(C.byref(a), stream), "cad_gemm_stream")
     return out
 
 
@@ -1017,7 +1074,7 @@ def proj_wxT_fp8(Wq: torch.Tensor, sw: torch.Tensor, Xq: torch.Tensor, sx: torch
 
 
 def proj_wx_wgrad_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
-    return X.dtype == torch.bfloat16 and bool(L.get_lib().cad_proj_wx_wgrad_supported(int(M), int(K), int(T)))
+    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wx_wgrad_supported(int(M), int(K), int(T)))
 
 
 def wgrad_partials(T: int, K: int, M: int, device, nsets: int = 1) -> torch.Tensor:
@@ -1035,21 +1092,21 @@ def proj_wx_wgrad(W: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, out: Option
     T = X.shape[1]
     if X.shape[0] != K or Y.shape != (M, T) or W.stride(1) != 1 or X.stride(1) != 1 or Y.stride(1) != 1:
         raise ValueError("proj_wx_wgrad: W (M, K), X (K, T), Y (M, T) with unit inner stride")
-    lib = L.get_lib()
+    _same_mfma_dtype(W, X, Y, out)
     if out is None:
-        out = torch.empty((M, T), dtype=torch.bfloat16, device=X.device)
+        out = torch.empty((M, T), dtype=X.dtype, device=X.device)
     own = part is None
     if own:
         part = wgrad_partials(T, K, M, X.device)[0]
     stream = L.stream_and_check(W, X, Y, out, part, contiguous=False)
     a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0), None, 0, None, 0,
                    L.ptr(Y), Y.stride(0), L.ptr(part))
-    L.check(lib.cad_proj_wx_wgrad(C.byref(a), stream), "cad_proj_wx_wgrad")
+    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
     return out, (part.sum(dim=0) if own else None)
 
 
 def proj_wgrad_only_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
-    return X.dtype == torch.bfloat16 and bool(L.get_lib().cad_proj_wgrad_only_supported(int(M), int(K), int(T)))
+    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wgrad_only_supported(int(M), int(K), int(T)))
 
 
 def proj_wgrad_only(X: torch.Tensor, Y: torch.Tensor, part: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -1059,11 +1116,11 @@ def proj_wgrad_only(X: torch.Tensor, Y: torch.Tensor, part: Optional[torch.Tenso
     M = Y.shape[0]
     if Y.shape[1] != T or X.stride(1) != 1 or Y.stride(1) != 1:
         raise ValueError("proj_wgrad_only: X (K, T), Y (M, T) with unit inner stride")
-    lib = L.get_lib()
+    _same_mfma_dtype(X, Y)
     own = part is None
     if own:
         part = wgrad_partials(T, K, M, X.device)[0]
     stream = L.stream_and_check(X, Y, part, contiguous=False)
     a = L.ProjArgs(None, L.ptr(X), None, T, M, K, 0, X.stride(0), 0, None, 0, None, 0, L.ptr(Y), Y.stride(0), L.ptr(part))
-    L.check(lib.cad_proj_wx_wgrad(C.byref(a), stream), "cad_proj_wx_wgrad")
+    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
     return part.sum(dim=0).t().contiguous() if own else None

@@ -34,7 +34,9 @@ extern "C" {
 #endif
 
 typedef enum { CAD_OK = 0, CAD_ERR_BAD_ARG = 1, CAD_ERR_UNSUPPORTED = 2, CAD_ERR_LAUNCH = 3 } cad_status;
-typedef enum { CAD_F32 = 0, CAD_BF16 = 1 } cad_dtype;
+/* CAD_F16: the opt-in fp16 activations (binary16 in HBM, fp32 arithmetic and accumulation inside the kernels, fp32 parameters -- the
+ * contract of the bf16 path).  Each entry point below names the *_dtype fields that accept it. */
+typedef enum { CAD_F32 = 0, CAD_BF16 = 1, CAD_F16 = 2 } cad_dtype;
 
 /* Library identification / error text (static strings). */
 const char* cad_version(void);
@@ -49,7 +51,7 @@ int cad_is_device_build(void);
  *   out[1][b][l][:] = W[comp[ids[b][l]]][:]                 strand 1 (t-frame: the reference's two flipL
  *                                                            cancel and its flipC is the storage convention)
  * Integer index path is exact.  ids: int64 (B, L).  comp: int64 (V) device, NULL when n_strands == 1.
- * W: (V, D) in w_dtype.  out: (n_strands, B, L, D) in out_dtype.
+ * W: (V, D) in w_dtype.  out: (n_strands, B, L, D) in out_dtype.  (w_dtype, out_dtype): any of F32 / BF16 pairs, (F32, F16), (F16, F16).
  * Returns CAD_ERR_BAD_ARG if an id is outside [0, V) (checked on device, reported via *err_flag if given). */
 typedef struct {
     const int64_t* ids;
@@ -61,7 +63,7 @@ typedef struct {
     int w_dtype, out_dtype;
 } cad_embed_args;
 int cad_embed_fwd(const cad_embed_args* a, void* stream);
-/* dW (V, D) fp32 is ACCUMULATED into (caller zeroes):  dW[ids] += dout[0], dW[comp[ids]] += dout[1]. */
+/* dW (V, D) fp32 is ACCUMULATED into (caller zeroes):  dW[ids] += dout[0], dW[comp[ids]] += dout[1].  dout_dtype: F32, BF16 or F16. */
 typedef struct {
     const int64_t* ids;
     const int64_t* comp;
@@ -90,7 +92,9 @@ int cad_embed_bwd_slots(const cad_embed_bwd_args* a);
  *   y[1-s][r][D-1-c], residual_out[1-s][r][D-1-c]  <-  token (s, r), channel c.
  * swap_flip = 0 is the un-fused / final-norm / Caduceus-Ph behaviour (identity map).
  * residual_in may be NULL (first layer).  residual_out (fp32) and rstd (S*R floats) [+ mean for LayerNorm] are
- * always written; they are what the backward needs.  weight/bias fp32 (bias NULL for RMSNorm). */
+ * always written; they are what the backward needs.  weight/bias fp32 (bias NULL for RMSNorm).
+ * (x_dtype, y_dtype), forward and backward: (F32, F32), (F32, BF16), (BF16, BF16), (F32, F16), (F16, F16); the e4m3 copy (y_fp8) is
+ * a bf16-path epilogue. */
 typedef struct {
     const void* x;
     const float* residual_in;
@@ -144,7 +148,7 @@ int cad_add_norm_bwd_slots(const cad_add_norm_bwd_args* a);
  * (modeling_caduceus.py:128,130).  In logical (direction-mapped) coordinates:
  *   out[p] = silu(bias + sum_k w[k] * x[p - (K-1) + k]),  zero padding before the logical start.
  * A right-to-left row is therefore the reference's flipL -> conv -> flipL without moving data.
- * x, out: (E, SB, L) in dtype.  w: (E, K) fp32, K in [1, 4].  bias: (E) fp32 or NULL. */
+ * x, out: (E, SB, L) in dtype (F32, BF16 or F16; the same for the backward's dout / dx).  w: (E, K) fp32, K in [1, 4].  bias: (E) fp32 or NULL. */
 typedef struct {
     const void* x;
     const float* w;
@@ -193,7 +197,7 @@ int cad_conv1d_bwd_slots(const cad_conv1d_bwd_args* a);
  * p is the logical position; physical l = p (left-to-right rows) or L-1-p (right-to-left rows).  The
  * right-to-left variant is an exact mirror (same chunk boundaries counted from the logical start, same
  * floating-point operation order), which is what keeps RC-equivariance bit-exact.
- * u, delta, z, out: (E, SB, L) dtype.  A: (E, N) fp32 (= -exp(A_log)).  Bm, Cm: (N, SB, L) dtype.
+ * u, delta, z, out: (E, SB, L) dtype (F32, BF16 or F16).  A: (E, N) fp32 (= -exp(A_log)).  Bm, Cm: (N, SB, L) dtype.
  * D, delta_bias: (E) fp32.  chunk_state: fp32 buffer of cad_scan_state_floats() elements (the running state at
  * every chunk start, needed by the backward), or NULL for inference.
  * Optional state carries, (E, SB, N) fp32, NULL = absent: h0 = state entering the row's first logical position (default 0),
@@ -231,7 +235,8 @@ int64_t cad_scan_chunk_len(void);
 int64_t cad_scan_state_floats(int E, int64_t SB, int64_t L, int N);
 /* Backward.  du, ddelta, dz are WRITTEN (dtype).  dA (E,N), dD (E), ddelta_bias (E) are ACCUMULATED with a few fp32
  * atomics per channel (caller zeroes).  dB, dC: n_partials = cad_scan_bwd_partials(E) slots of (N,SB,L) each, in the
- * activation dtype (fp32 mode: fp32 slots; bf16 mode: bf16 slots, each holding an fp32-accumulated 8-channel sum);
+ * activation dtype (fp32 mode: fp32 slots; bf16 mode: bf16 slots, each holding an fp32-accumulated 8-channel sum; fp16 mode: BF16
+ * slots as in bf16 mode -- sums of loss-scaled gradients never pass through binary16's range before the fold);
  * slot k is WRITTEN (plain coalesced stores, no atomics, no zeroing needed) with the sum over the channels of workgroup
  * k; cad_reduce_partials folds the slots (fp32 accumulation) into the final (N,SB,L) gradient.
  * chunk_state: as written by the forward.  out: the forward's (gated) output, required when z != NULL: the gate gradient
@@ -294,7 +299,8 @@ int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void* stream);
 int cad_scan_bwd_gate_fix(const cad_scan_bwd_args* sets, int nsets, void* stream);
 int64_t cad_scan_gate_fix_entries(int E, int64_t SB, int64_t L);
 int cad_scan_bwd_partials(int E);
-/* dst[i] = sum_k src[k*n + i], k < n_partials (fp32 accumulation); src and dst in dtype (fp32 or bf16). */
+/* dst[i] = sum_k src[k*n + i], k < n_partials (fp32 accumulation); dst in dtype; src in dtype for F32 / BF16, in bf16 for F16 (the scan
+ * backward's fp16-mode slots). */
 int cad_reduce_partials(const void* src, int n_partials, int64_t n, void* dst, int dtype, void* stream);
 /* The same fold for up to CAD_REDUCE_MAX_JOBS (src, dst) pairs of equal depth, length and dtype in ONE launch -- the dB and dC slots of
  * both parameter sets of a BiMamba layer (four folds per layer; same summation order as the single fold: bit-identical results). */
@@ -378,12 +384,17 @@ typedef struct {
 } cad_proj_args;
 #define CAD_ACT_SOFTPLUS_BIAS 1
 int cad_proj_wxT(const cad_proj_args* a, void* stream);
+/* Every cad_proj_* / cad_gemm_stream entry point has an fp16 sibling taking the same struct: all operands binary16 instead of bf16
+ * (v_mfma_f32_16x16x32_f16, fp32 accumulation, results rounded to nearest even, +-inf on overflow).  The *_supported / *_partials
+ * queries apply to both element types. */
+int cad_proj_wxT_f16(const cad_proj_args* a, void* stream);
 int cad_proj_supported(int K);
 /* cad_proj_wx:  out (M, T) = W (M, K) . X (K, T) [+ acc],  all channel-major, thin K (cad_proj_wx_supported: K <= 64,
  * K % 8 == 0, T % 8 == 0) -- dt_proj (K = dt_rank; `dt_proj` inside mamba_inner_fn) and the x_proj input gradient
  * d(xc) = du + W_x^T . d(dbc) of its backward.  X is token-contiguous: the MFMA fragments are transposed on the way out
  * of LDS (ds_read_b64_tr_b16). */
 int cad_proj_wx(const cad_proj_args* a, void* stream);
+int cad_proj_wx_f16(const cad_proj_args* a, void* stream);
 int cad_proj_wx_supported(int K, int64_t T);
 /* cad_proj_wx also takes thin M / deep K products (M <= 64, K a multiple of 64 up to 1024, T % 8 == 0; ldo % 4; W (M x K) and the
  * ring of X tiles must fit the 160 KB of LDS): x_proj (M = dt_rank + 2 d_state, K = d_inner; `x_proj` inside mamba_inner_fn) and
@@ -397,6 +408,7 @@ int cad_proj_wx_thin_supported(int M, int K, int64_t T);
  * tail block), bf16.  wg_partials: cad_proj_wx_wgrad_partials(T) slots of
  * (K, M) fp32, one per workgroup, WRITTEN (no zeroing needed); dW = the sum over the slots (fixed order: deterministic). */
 int cad_proj_wx_wgrad(const cad_proj_args* a, void* stream);
+int cad_proj_wx_wgrad_f16(const cad_proj_args* a, void* stream);  /* (also the weight-gradient-only form: W == NULL, out == NULL) */
 int cad_proj_wx_wgrad_supported(int M, int K, int64_t T);
 /* With W == NULL and out == NULL the same entry point computes the weight gradient alone, for any M <= 64
  * (cad_proj_wgrad_only_supported; the same T >= 128, T % 128 == 0): dW_x = xc . d(dbc)^T of the x_proj backward
@@ -419,6 +431,7 @@ typedef struct {
     int64_t ldw, ldx, ldo;
 } cad_proj_tm_args;
 int cad_proj_xTw(const cad_proj_tm_args* a, void* stream);
+int cad_proj_xTw_f16(const cad_proj_tm_args* a, void* stream);
 int cad_proj_xTw_supported(int M, int K, int64_t T);
 
 /* ---------------------------------------------------------------------------------------------------------
@@ -452,6 +465,7 @@ typedef struct {
     int col_fastest;
 } cad_gemm_stream_args;
 int cad_gemm_stream(const cad_gemm_stream_args* a, void* stream);
+int cad_gemm_stream_f16(const cad_gemm_stream_args* a, void* stream);  /* CAD_GEMM_OUT_T_BF16 mode: the token-major result in fp16 */
 
 /* cad_fold_f32_multi: up to CAD_FOLD_F32_MAX_JOBS sums of fp32 partial tiles in ONE launch -- the per-workgroup / per-K-slice partials of the
  * weight-gradient kernels of a mixer layer's backward (cad_gemm_stream's CAD_GEMM_PARTIALS slices, cad_proj_wx_wgrad's slots), which were
@@ -525,7 +539,7 @@ int cad_proj_fp8_supported(int K);
  * RCPS LM head + cross-entropy.   Replaces RCPSLMHead.forward (modeling_rcps.py:233-246), logits.float()
  * (modeling_caduceus.py:475) and cross_entropy(ignore_index) (modeling_caduceus.py:279-283,
  * src/tasks/metrics.py:181-184).  t-frame:  logits[b,l,v] = <W[v], t1[b,l]> + <W[comp[v]], t2[b,l]>.
- * hidden: (S, B*L, D) dtype.  W: (V, D) fp32.  logits: (B*L, V) fp32 (always written).
+ * hidden: (S, B*L, D) dtype (F32, BF16 or F16; the backward's dhidden likewise).  W: (V, D) fp32.  logits: (B*L, V) fp32 (always written).
  * If labels != NULL: loss_sum[0] += sum over tokens with label != ignore_index of -log softmax[label],
  * count[0] += number of such tokens (both ACCUMULATED; caller zeroes; loss = loss_sum / count).
  * block_partials: scratch of cad_lm_head_partials(rows) floats, or NULL.  With it the sum is DETERMINISTIC (one slot per
