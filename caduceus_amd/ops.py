@@ -379,6 +379,13 @@ def fold_side_available(device) -> bool:
 FOLD_GIVE_UPS = None  # a list: every device launch appends the number of give-up records (a device scalar) of its concurrent pass
 
 
+def _count_give_ups(give_ups):
+    """Diagnostics (tests, tools): the slices the concurrent pass left to the cleanup.  The records are int32 (chunk + 1) -- counted on
+    the integer view: read as fp32 they are denormals, which a flush-to-zero count would miss."""
+    if FOLD_GIVE_UPS is not None and give_ups is not None:
+        FOLD_GIVE_UPS.append(torch.count_nonzero(give_ups.view(torch.int32)))
+
+
 def fold_behind_scan(lib, fold_args, nsets: int, device, launch_scan, give_ups=None):
     """launch_scan() enqueues cad_scan_bwd_multi (with fold_counters set) on the current stream; the fold is enqueued on a second stream
     right behind it so that the two kernels run side by side (the fold's workgroups -- 48 VGPRs, 8 KB of LDS -- fit on the CUs next to
@@ -387,6 +394,7 @@ def fold_behind_scan(lib, fold_args, nsets: int, device, launch_scan, give_ups=N
     if not L.is_device_build():
         out = launch_scan()
         L.check(lib.cad_fold_partials_stream(fold_args, nsets, 0, None), "cad_fold_partials_stream (concurrent)")
+        _count_give_ups(give_ups)
         L.check(lib.cad_fold_partials_stream(fold_args, nsets, 1, None), "cad_fold_partials_stream (cleanup)")
         return out
     side, ev_ready, ev_done = _fold_side(device)
@@ -397,8 +405,7 @@ def fold_behind_scan(lib, fold_args, nsets: int, device, launch_scan, give_ups=N
     L.check(lib.cad_fold_partials_stream(fold_args, nsets, 0, C.c_void_p(side.cuda_stream)), "cad_fold_partials_stream (concurrent)")
     ev_done.record(side)
     main.wait_event(ev_done)
-    if FOLD_GIVE_UPS is not None and give_ups is not None:  # diagnostics (tests, tools): slices the concurrent pass left to the cleanup
-        FOLD_GIVE_UPS.append(torch.count_nonzero(give_ups))
+    _count_give_ups(give_ups)
     L.check(lib.cad_fold_partials_stream(fold_args, nsets, 1, C.c_void_p(main.cuda_stream)), "cad_fold_partials_stream (cleanup)")
     return out
 

@@ -73,3 +73,30 @@ def conv_fwd_c(x, w, bias):
     lib().cad_oracle_conv_fwd(_p(x_), _p(w_), _p(b_), _p(out), C.c_int64(nb), C.c_int64(E), C.c_int64(L),
                               C.c_int64(w_.shape[1]))
     return out
+
+
+def scan_bwd_sums_f64(u, delta, A, Bm, Cm, D, z, bias, dout, rev, W: int, delta_is_dt: bool = False, want_slots: bool = False):
+    """fp64 scan backward in the kernel's layout (u, delta, z, dout: (E, SB, L); Bm, Cm: (N, SB, L); rev: one flag per row) with the
+    channel sums of dB / dC split the way the kernel's partial slots split them (groups of W channels).  Returns a dict of CPU tensors:
+    dB / dC: (S, Ag, Ae) = (exact sum, sum of |group sums|, sum of |channel terms|); dA / dD / dbias: (sum, sum of |terms|);
+    du, ddelta, dz (fp32, dz None without a gate); dB_slots / dC_slots: (per-slot sums, their sums of |terms|), each
+    (G, N, SB, L), if want_slots."""
+    f = lambda t: None if t is None else t.detach().float().contiguous().cpu()
+    u, delta, A, Bm, Cm, D, z, bias, dout = map(f, (u, delta, A, Bm, Cm, D, z, bias, dout))
+    E, SB, L = u.shape
+    N = A.shape[1]
+    G = (E + W - 1) // W
+    rv = torch.tensor([int(r) for r in rev], dtype=torch.int32)
+    assert rv.numel() == SB and N <= 64
+    d64 = lambda *s: torch.empty(s, dtype=torch.float64)
+    bc = [d64(N, SB, L) for _ in range(6)]
+    pe = [d64(E, N), d64(E, N), d64(E), d64(E), d64(E), d64(E)]
+    du, dd = torch.empty_like(u), torch.empty_like(u)
+    dz = torch.empty_like(u) if z is not None else None
+    slots = [d64(G, N, SB, L) for _ in range(4)] if want_slots else [None] * 4
+    rc = lib().cad_oracle_scan_bwd_sums_f64(*map(_p, (u, delta, A, Bm, Cm, D, z, bias, dout, rv)), C.c_int(int(bool(delta_is_dt))),
+                                            C.c_int64(SB), C.c_int64(E), C.c_int64(L), C.c_int64(N), C.c_int64(W),
+                                            *map(_p, bc), *map(_p, pe), _p(du), _p(dd), _p(dz), *map(_p, slots))
+    assert rc == 0, "cad_oracle_scan_bwd_sums_f64: scratch allocation failed"
+    return dict(dB=tuple(bc[0:3]), dC=tuple(bc[3:6]), dA=(pe[0], pe[1]), dD=(pe[2], pe[3]), dbias=(pe[4], pe[5]), du=du, ddelta=dd,
+                dz=dz, dB_slots=(slots[0], slots[2]), dC_slots=(slots[1], slots[3]))

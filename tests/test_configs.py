@@ -374,6 +374,12 @@ def test_config4_one_layer_d512_L262144_every_gradient_vs_oracle(fp8):
     for k, e in errs.items():
         if not k.endswith("x_proj.weight"):
             assert e < bound_grad, (k, e)
+    # end to end as well: each direction's x_proj.weight error relative to the LARGER of the two directions' gradient norms (the
+    # cancellation over the tokens makes mamba_fwd's four times smaller in norm; the operand noise is the same in absolute terms)
+    xnorm = max(float(sd[k].grad.norm()) for k in names)
+    for k in names:
+        e = errs[k] * float(sd[k].grad.norm()) / xnorm
+        assert e < bound_grad, (k, e)
 
 
 def test_ph_L131072_lsplit_training_step_matches_unsplit(monkeypatch):

@@ -80,6 +80,31 @@ def test_fold_stream_bit_identical_to_reduce_partials(backend, G, N, SB, L, spli
     assert torch.equal(out, want) and int(aborts.abs().sum()) == 0
 
 
+@pytest.mark.parametrize("G,N,SB,L,split", [(64, 16, 2, 2 * CHUNK, 1), (8, 16, 1, 3 * CHUNK, 0)])
+def test_fold_behind_scan_counts_give_up_records(backend, monkeypatch, G, N, SB, L, split):
+    """ops.fold_behind_scan with a no-op scan and one chunk of row 0 left one arrival short: every slice of that row gives up at that
+    chunk, FOLD_GIVE_UPS receives exactly that many records -- counted on the int32 records (chunk + 1, fp32 denormals if read as floats:
+    a flush-to-zero count would report none) -- and the cleanup pass completes the fold."""
+    name, dev = backend
+    lib = CL.get_lib()
+    slots = _slots(dev, G, N, SB, L, seed=3 * G + SB)
+    stream = CL.stream_and_check(slots)
+    want = _reference_fold(lib, slots, G, N, SB, L, stream)
+    nch = L // CHUNK
+    out = torch.full_like(want, float("nan"))
+    cflat = torch.zeros((int(lib.cad_scan_bwd_fold_counter_ints(SB, L)),), dtype=torch.int32, device=dev)
+    counters = cflat[:SB * nch].view(SB, nch)
+    counters.fill_(G)
+    counters[0, nch - 1 if nch == 1 else nch - 2] = G - 1
+    cflat[SB * nch] = G * SB
+    give_ups = torch.zeros((1, SB, G), dtype=torch.int32, device=dev)
+    a = _fold_args(slots, out, counters, give_ups[0], G, N, SB, L, split, 0, 1)
+    monkeypatch.setattr(ops, "FOLD_GIVE_UPS", [])
+    ops.fold_behind_scan(lib, a, 1, slots.device, lambda: None, give_ups=give_ups)
+    assert [int(x) for x in ops.FOLD_GIVE_UPS] == [G]
+    assert torch.equal(out, want) and int(give_ups.abs().sum()) == 0
+
+
 def test_fold_stream_shapes_refused():
     from caduceus_amd import _lib
     lib = _lib.get_lib()
