@@ -27,6 +27,14 @@ template <>
 struct cad_is_bf16<bf16_t> {
     static constexpr bool value = true;
 };
+template <typename T>
+struct cad_is_f16 {
+    static constexpr bool value = false;
+};
+template <>
+struct cad_is_f16<f16_t> {
+    static constexpr bool value = true;
+};
 
 __device__ __forceinline__ float cad_bits2f(uint32_t u) {
     union {

@@ -105,6 +105,24 @@ __device__ __forceinline__ void sc_slot_store16(void* p, u32x4 v) {
 #endif
 }
 
+// The gate gradient recovers  y sigmoid(z) = out / z  from the STORED output.  A gate is LOST where that quotient cannot be formed:
+//   * fp32 / bf16: |z| < 2^-100 -- z == 0 (out == 0), and the smallest gates, whose 1 / z leaves fp32's range (0 * inf, or inf).  At
+//     2^-100 and above an fp32-range output is normal unless |y| < 2^-25, where what is lost is < 2^-49.
+//   * fp16: |z| <= 2^-15.  The stored out = y z sigmoid(z) is subnormal for |y z| < 2^-13: its absolute rounding floor 2^-25, divided
+//     by z, is an error of  2^-25 |dout| / |z|  in dz -- |dout y| / 2 at the smallest gates.  Above 2^-15 that is < 2^-10 |dout|, a
+//     quarter of the fp16 tolerance class's absolute term (4e-3) per unit of dout; at 2^-15 and below the position is recomputed.
+//     The criterion is the gate alone (not the stored output): every set sharing the gate lists the same positions without reading
+//     another tensor, and the kernel's per-item work is that of the z == 0 test.  With z ~ N(0, 1), 2.4e-5 of the gates qualify,
+//     i.e. ~1.2 % of the 512-position chunks.
+// A lost position contributes 0 in the main kernel and puts its chunk on the worklist; cad_scan_bwd_gate_fix recomputes y there and adds
+// dout * y * sigmoid(z) * (1 + z (1 - sigmoid(z)))  (= dout * y / 2 at z == 0, and to fp32 rounding below 2^-100).
+#define SC_GATE_TINY 7.888609052210118e-31f   // 2^-100
+#define SC_GATE_TINY_F16 3.0527e-05f          // just above 2^-15 = 3.0518e-5 (the next binary16 is 3.0547e-5): |z| <= 2^-15
+template <typename T>
+__device__ __forceinline__ bool sc_gate_lost(float z) {
+    return __builtin_fabsf(z) < (cad_is_f16<T>::value ? SC_GATE_TINY_F16 : SC_GATE_TINY);
+}
+
 __device__ __forceinline__ f32x2 wave_sum2(f32x2 v) { return f2(wave_sum_dpp(v[0]), wave_sum_dpp(v[1])); }
 
 // sigmoid(raw delta) recovered from dt = softplus(raw delta): 1 - exp(-dt).  Results that are rounded to bf16 take the two-term series
@@ -322,12 +340,12 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 float zz[SC_S];
                 sc_unpack_p<T, SC_S>(z_raw, rev, dsel, zz);
                 if (a.gate_fix_list) {
-                    // out / z cannot recover y where the gate is exactly 0 (out == 0 there): remember the chunk, the fix-up launch
-                    // (cad_scan_bwd_gate_fix) recomputes y for it and adds dout * y / 2 to dz.  min |z| over the lane's items == 0.
+                    // out / z cannot recover y where the gate is lost (sc_gate_lost: 0, or too small for 1 / z): remember the chunk, the fix-up
+                    // launch (cad_scan_bwd_gate_fix) recomputes y for it and adds dout * y / 2 to dz.  min |z| over the lane's items.
                     float zmin = __builtin_fabsf(zz[0]);
 #pragma unroll
                     for (int i = 1; i < SC_S; ++i) zmin = __builtin_fminf(zmin, __builtin_fabsf(zz[i]));
-                    if (cad_wave_any(zmin == 0.f && p0 < L && act) && lane == 0) {
+                    if (cad_wave_any(zmin < SC_GATE_TINY && p0 < L && act) && lane == 0) {
                         const int slot = atomicAdd(a.gate_fix_count, 1);
                         a.gate_fix_list[slot] = (int64_t)e | ((int64_t)sb << 20) | ((int64_t)c << 40);
                     }
@@ -344,8 +362,8 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
 #pragma unroll
                     for (int i = 0; i < SC_S; ++i) {
                         const float sg = cad_sigmoid(zz[i]);
-                        // (legacy product: 0 where out == 0, i.e. also at z == 0 where 1 / z is inf -- the value the fix-up launch adds to)
-                        const float ys = cad_mul_legacy(oo[i], cad_rcp(zz[i]));
+                        // (0 at a lost gate -- the value the fix-up launch adds to; legacy product: an output that is 0 stays 0)
+                        const float ys = cad_mul_legacy(oo[i], __builtin_fabsf(zz[i]) < SC_GATE_TINY ? 0.f : cad_rcp(zz[i]));
                         const float silu = zz[i] * sg;
                         dzv[i] = dy[i] * ys * ((1.f + zz[i]) - silu);
                         dy[i] *= silu;
@@ -375,11 +393,11 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 float zz[SC_S], oo[SC_S], dzv[SC_S];
                 sc_unpack<T, SC_S>(z_raw, rev, zz);
                 if (!CO && a.gate_fix_list) {
-                    // out / z cannot recover y where the gate is exactly 0 (out == 0 there): remember the chunk, the
-                    // fix-up launch (cad_scan_bwd_gate_fix) recomputes y for it and adds dout * y / 2 to dz
+                    // out / z cannot recover y where the gate is lost (sc_gate_lost): remember the chunk, the fix-up
+                    // launch (cad_scan_bwd_gate_fix) recomputes y for it and adds the gate gradient to dz
                     int z0 = 0;  // (bitwise, not short-circuit: no branch per item)
 #pragma unroll
-                    for (int i = 0; i < SC_S; ++i) z0 |= (int)(zz[i] == 0.f) & (int)(p0 + i < L);
+                    for (int i = 0; i < SC_S; ++i) z0 |= (int)sc_gate_lost<T>(zz[i]) & (int)(p0 + i < L);
                     if (cad_wave_any(z0 != 0 && act) && lane == 0) {
                         const int slot = atomicAdd(a.gate_fix_count, 1);
                         a.gate_fix_list[slot] = (int64_t)e | ((int64_t)sb << 20) | ((int64_t)c << 40);
@@ -401,7 +419,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                     for (int i = 0; i < SC_S; ++i) {
                         const float sg = cad_sigmoid(zz[i]);
                         const float yq = oo[i] * cad_rcp(zz[i]);
-                        const float ys = (zz[i] == 0.f) ? 0.f : yq;
+                        const float ys = sc_gate_lost<T>(zz[i]) ? 0.f : yq;
                         dzv[i] = dy[i] * ys * (1.f + zz[i] * (1.f - sg));
                         dy[i] *= zz[i] * sg;
                     }
@@ -803,11 +821,12 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
     }
 }
 
-// Gate gradient where z == 0 exactly (see the worklist in scan_bwd_kernel): one WORKGROUP per recorded (channel, row, chunk)
-// recomputes the UNGATED y of that chunk from the saved chunk state (serial scan + DPP wave scan, as the forward) and
-// adds  dout * y * sigmoid(0) = dout * y / 2  to dz at the positions whose gate is 0.  Rare path: element-wise loads.
-// (Rare per element, not per launch: 134 M gate values per configs[2] launch and P(an fp32 sum rounds to 0) ~ 4e-9 make about one
-// entry per two launches.)  The four waves share the state pairs -- the path is a chain of dependent global round trips, one per
+// Gate gradient where the gate is lost (sc_gate_lost; see the worklist in scan_bwd_kernel): one WORKGROUP per recorded (channel, row,
+// chunk) recomputes the UNGATED y of that chunk from the saved chunk state (serial scan + DPP wave scan, as the forward) and adds the
+// gate gradient to dz at the lost positions: dout * y / 2 for fp32 / bf16 (z == 0 or below 2^-100), the full
+// dout * y * sigmoid(z) (1 + z (1 - sigmoid(z)))  for fp16's |z| <= 2^-15.  Rare path: element-wise loads.
+// (Rare per element, not per launch.  bf16: 134 M gate values per configs[2] launch and P(an fp32 sum rounds to 0) ~ 4e-9 make about
+// one entry per two launches.  fp16: 2.4e-5 of N(0, 1) gates, ~1.2 % of the chunks -- some 3000 entries at that shape.)  The four waves share the state pairs -- the path is a chain of dependent global round trips, one per
 // state pair -- and their partial y are added in a fixed order through LDS.
 #define GF_WAVES 4
 template <typename T>
@@ -890,8 +909,16 @@ __global__ __launch_bounds__(64 * GF_WAVES) void scan_gate_fix_kernel(cad_scan_b
                 for (int w = 0; w < GF_WAVES - 1; ++w) y[i] += ypart[w][i][lane];
                 if (p0 + i < L) {
                     const int64_t l = cad_phys(p0 + i, L, rev);
-                    if (to_f32(z_row[l]) == 0.f)
-                        dz_row[l] = from_f32<T>(to_f32(dz_row[l]) + 0.5f * to_f32(g_row[l]) * y[i]);
+                    const float zv = to_f32(z_row[l]);
+                    if (sc_gate_lost<T>(zv)) {
+                        if constexpr (cad_is_f16<T>::value) {
+                            const float sg = cad_sigmoid(zv);
+                            const float coef = zv == 0.f ? 0.5f : sg * (1.f + zv * (1.f - sg));
+                            dz_row[l] = from_f32<T>(to_f32(dz_row[l]) + coef * to_f32(g_row[l]) * y[i]);
+                        } else {
+                            dz_row[l] = from_f32<T>(to_f32(dz_row[l]) + 0.5f * to_f32(g_row[l]) * y[i]);
+                        }
+                    }
                 }
             }
         }
@@ -1241,6 +1268,11 @@ extern "C" int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void
         CAD_CHECK_ARG(a->z != nullptr || a->dz == nullptr);               // dz needs the gate; dz == NULL: not wanted here
         CAD_CHECK_ARG(a->dz == nullptr || a->out != nullptr);
         CAD_CHECK_ARG(a->out2 == nullptr || a->dz != nullptr);
+        if (a->out2 && a->gate_fix_list) {  // this set writes 0 at a lost gate for BOTH scans: the set that owns out2 must list it too
+            bool listed = false;
+            for (int j = 0; j < nsets; ++j) listed = listed || (j != i && sets[j].out == a->out2 && sets[j].gate_fix_list != nullptr);
+            CAD_CHECK_ARG(listed);
+        }
         CAD_CHECK_ARG(a->E > 0 && a->SB > 0 && a->L > 0 && a->N > 0 && a->N <= SC_NMAX);
         CAD_CHECK_ARG(a->split >= 0 && a->split <= a->SB && a->SB <= 65535);
         CAD_CHECK_ARG(a->carry_only || a->n_partials == cad_scan_bwd_partials(a->E));
@@ -1332,8 +1364,10 @@ extern "C" int cad_scan_bwd_gate_fix(const cad_scan_bwd_args* sets, int nsets, v
         CAD_CHECK_ARG(a->E <= (1 << 20) && a->SB <= (1 << 20));
         // an empty or one-entry worklist as a rule (bf16 products: P(z == 0) ~ 4e-9) -- but thousands of entries per launch behind the fp8
         // in_proj, whose sums of few-bit products cancel EXACTLY far more often: 32 workgroups took 120 us per launch there (3.8 ms per
-        // configs[4] step, profiles/r06_step_trace_c4_fp8.txt), one per CU takes the list in parallel; idle workgroups leave at once
-        dim3 grid((unsigned)cad_cu_count()), block(64 * GF_WAVES);
+        // configs[4] step, profiles/r06_step_trace_c4_fp8.txt), and thousands in fp16 mode (gates up to 2^-15): two per CU -- the kernel's
+        // ~184 VGPRs let two of its four-wave workgroups share a CU, and an entry is a chain of dependent loads -- take the list in
+        // parallel; idle workgroups leave at once
+        dim3 grid((unsigned)(2 * cad_cu_count())), block(64 * GF_WAVES);
         if (a->dtype == CAD_F32)
             CAD_LAUNCH((scan_gate_fix_kernel<float>), grid, block, 0, stream, *a);
         else if (a->dtype == CAD_BF16)

@@ -483,7 +483,7 @@ class BiMambaMixerFn(torch.autograd.Function):
             _keep = ops.fold_behind_scan(lib, fargs, 2, x2d.device, launch_scan, give_ups=zbuf[13])
         else:
             _keep = launch_scan()
-        L.check(lib.cad_scan_bwd_gate_fix(args, 2, stream), "cad_scan_bwd_gate_fix")  # no-op unless some z == 0 exactly
+        L.check(lib.cad_scan_bwd_gate_fix(args, 2, stream), "cad_scan_bwd_gate_fix")  # no-op unless some gate is lost (z == 0; fp16: |z| <= 2^-15)
         grads, dxcs, part = [], [], []
         if not stream_fold:
             # ... by one launch behind the scan (four folds: cad_reduce_partials_multi)

@@ -411,7 +411,8 @@ def fold_behind_scan(lib, fold_args, nsets: int, device, launch_scan, give_ups=N
 
 
 def gate_fix_buffers(lib, u, N):
-    """Worklist (int64 slots) + zeroed counter (int32) for the exact gate gradient at z == 0 (cad_scan_bwd_gate_fix)."""
+    """Worklist (int64 slots) + zeroed counter (int32) for the exact gate gradient at lost gates (cad_scan_bwd_gate_fix): z == 0 and
+    |z| < 2^-100; in fp16 every |z| <= 2^-15 (~1 % of the chunks of N(0, 1) gates)."""
     E, SB, Lq = u.shape
     lst = torch.empty((lib.cad_scan_gate_fix_entries(E, SB, Lq),), dtype=torch.int64, device=u.device)
     cnt = torch.zeros((1,), dtype=torch.int32, device=u.device)
@@ -487,7 +488,7 @@ class _ScanMulti(torch.autograd.Function):
             keep.append((dout, dBC, fix_list, fix_cnt))
             res.append([du, ddelta, dA, dBC, dD, dbias, dz])
         keep.append(scan_bwd_launch(lib, args, nsets, stream, k, Ps, dirs, split))
-        if z is not None:  # exact gate gradient where z == 0 (rare; the launch is a no-op otherwise)
+        if z is not None:  # exact gate gradient at lost gates (z == 0: rare, the launch is a no-op otherwise; fp16: |z| <= 2^-15)
             L.check(lib.cad_scan_bwd_gate_fix(args, nsets, stream), "cad_scan_bwd_gate_fix")
         grads = []
         dz_tot = None

@@ -240,12 +240,16 @@ int64_t cad_scan_state_floats(int E, int64_t SB, int64_t L, int N);
  * slot k is WRITTEN (plain coalesced stores, no atomics, no zeroing needed) with the sum over the channels of workgroup
  * k; cad_reduce_partials folds the slots (fp32 accumulation) into the final (N,SB,L) gradient.
  * chunk_state: as written by the forward.  out: the forward's (gated) output, required when z != NULL: the gate gradient
- * uses y = out / silu(z) instead of re-accumulating y.  Where z == 0 EXACTLY that quotient is 0/0: the kernel writes 0
- * there and, when gate_fix_list / gate_fix_count are given, records the (channel, row, chunk) in the list;
- * cad_scan_bwd_gate_fix (same argument structs, called after cad_scan_bwd[_multi] on the same stream) recomputes y for
- * the recorded chunks and adds the exact dout * y / 2 into gate_fix_dz (= dz, or the dz buffer of the set that shares the
- * gate).  gate_fix_list: cad_scan_gate_fix_entries(E, SB, L) int64 slots; gate_fix_count: one int32 the caller zeroes.
- * Without them dz stays 0 where z == 0.
+ * uses y = out / silu(z) instead of re-accumulating y.  Where z == 0 EXACTLY that quotient is 0/0 (and below |z| = 2^-100 the
+ * reciprocal leaves fp32's range): the kernel writes 0 there and, when gate_fix_list / gate_fix_count are given, records the
+ * (channel, row, chunk) in the list; cad_scan_bwd_gate_fix (same argument structs, called after cad_scan_bwd[_multi] on the same
+ * stream) recomputes y for the recorded chunks and adds the exact dout * y / 2 into gate_fix_dz (= dz, or the dz buffer of the set
+ * that shares the gate).  gate_fix_list: cad_scan_gate_fix_entries(E, SB, L) int64 slots; gate_fix_count: one int32 the caller
+ * zeroes.  Without them dz stays 0 where z == 0.
+ * fp16 mode: a stored output under a gate |z| <= 2^-15 is subnormal (rounding floor 2^-25, divided by z: an error of up to
+ * |dout y| / 2 in dz), so these gates count as lost like z == 0: 0 from the kernel, and the fix-up launch adds the full
+ * dout * y * sigmoid(z) * (1 + z (1 - sigmoid(z))).  The worklist capacity is unchanged (entries are per chunk).  A set that passes
+ * out2 together with a worklist writes 0 at a lost gate for both scans: the set that owns out2 must carry a worklist too (checked).
  * Optional carries (E, SB, N) fp32: dhT = gradient w.r.t. the forward's hT (default 0), dh0 = gradient w.r.t. h0 (written).
  * Shared gate (BiMamba: the forward and the reverse scan are gated by the same z and receive the same dout): pass the
  * other scan's gated output as out2 and dz receives the gate gradient of BOTH scans (one fp32 evaluation, one rounding);

@@ -197,9 +197,19 @@ def test_selective_scan_golden_f16(backend, shape, golden_dir):
 @pytest.mark.parametrize("cut", [300, 512])
 def test_scan_carries_f16(backend, cut):
     """h0 / hT / dhT / dh0 in fp16 mode: a row scanned as two chained segments equals the row scanned at once."""
+    _scan_carries_f16(backend, cut, "suite")
+
+
+@pytest.mark.parametrize("cut", [300, 512])
+def test_scan_carries_f16_long_memory(backend, cut):
+    """... with inputs whose state outlives the cut (regime "long_memory" of test_kernels._scan_inputs)."""
+    _scan_carries_f16(backend, cut, "long_memory")
+
+
+def _scan_carries_f16(backend, cut, regime):
     _, dev = backend
     E, SB, L, N = 5, 1, 1100, 16
-    t = _scan_inputs(E, SB, L, N, 31, dev, F16)
+    t = _scan_inputs(E, SB, L, N, 31, dev, F16, regime)
     order = ("u", "delta", "A", "B", "C", "D", "z", "bias")
     act = {"u", "delta", "B", "C", "z"}
     mk = lambda: [leaf(t[k], dev, F16 if k in act else torch.float32) for k in order]

@@ -41,11 +41,22 @@ SCAN_CASES = [  # E, SB, L, N, split, rev_lo, rev_hi
 ]
 
 
-def _scan_inputs(E, SB, L, N, seed, device, dtype):
+def _scan_inputs(E, SB, L, N, seed, device, dtype, regime="suite"):
+    """regime "suite": A = -(0.5 + 15.5 rand), dt = softplus(randn + randn - 3) -- the state is forgotten inside one 512-position chunk, so
+    carries across chunks, segments and ranks are multiplied by ~0.  regime "long_memory": A = -(0.02 + rand) (every fourth state keeps
+    the fast suite range), dt = softplus(0.3 randn + 0.3 randn - 5.5) ~ 4e-3 -- the decay product of a chunk is of order one, as in a
+    released model (A = -(1..N), dt log-uniform in [1e-3, 1e-1]).  The measured decay products of both recipes are in the docstring of
+    tests/test_scan_regimes.py, which asserts the long-memory conditions per case (assert_long_memory)."""
     g = torch.Generator().manual_seed(seed)
     r = lambda *s: torch.randn(*s, generator=g)
     t = dict(u=r(E, SB, L), delta=r(E, SB, L), A=-(0.5 + 15.5 * torch.rand(E, N, generator=g)), B=r(N, SB, L),
              C=r(N, SB, L), D=r(E), z=r(E, SB, L), bias=r(E) - 3.0, w=r(E, SB, L))
+    if regime == "long_memory":
+        slow = -(0.02 + torch.rand(E, N, generator=g))
+        slow[:, 3::4] = t["A"][:, 3::4]
+        t["A"], t["delta"], t["bias"] = slow, 0.3 * t["delta"], 0.3 * (t["bias"] + 3.0) - 5.5
+    else:
+        assert regime == "suite", regime
     for k in ("u", "delta", "B", "C", "z", "w"):
         t[k] = t[k].to(dtype).float()  # oracle sees exactly the values the kernel sees
     return t
@@ -300,9 +311,20 @@ def test_causal_conv1d_two_sets(backend, case, dtype):
 def test_scan_state_carries_chain_segments(backend, dtype, cut):
     """h0 / hT / dhT / dh0 of cad_scan_fwd / cad_scan_bwd: a row scanned as two chained segments (each direction gets
     the segments in its own order) equals the row scanned at once, outputs and every gradient."""
+    _state_carries_chain_segments(backend, dtype, cut, "suite")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("cut", [512, 700, 37])
+def test_scan_state_carries_chain_segments_long_memory(backend, dtype, cut):
+    """... where the state survives the cut by thousands of positions (regime "long_memory" of _scan_inputs)."""
+    _state_carries_chain_segments(backend, dtype, cut, "long_memory")
+
+
+def _state_carries_chain_segments(backend, dtype, cut, regime):
     name, dev = backend
     E, SB, L, N = 5, 2, 1100, 16
-    t = _scan_inputs(E, SB, L, N, 31, dev, dtype)
+    t = _scan_inputs(E, SB, L, N, 31, dev, dtype, regime)
     order = ("u", "delta", "A", "B", "C", "D", "z", "bias")
     act = {"u", "delta", "B", "C", "z"}
     mk = lambda: [leaf(t[k], dev, dtype if k in act else torch.float32) for k in order]
@@ -502,6 +524,17 @@ def test_fused_softplus_rounding_point_against_oracle(backend, case):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("k", [2, 4])
 def test_scan_lsplit_two_pass_matches_unsplit_and_oracle(backend, monkeypatch, dtype, k):
+    _lsplit_two_pass(backend, monkeypatch, dtype, k, "suite")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("k", [2, 4])
+def test_scan_lsplit_two_pass_matches_unsplit_and_oracle_long_memory(backend, monkeypatch, dtype, k):
+    """... where the decay product P of a segment is of order one, so the composition of the segment maps matters."""
+    _lsplit_two_pass(backend, monkeypatch, dtype, k, "long_memory")
+
+
+def _lsplit_two_pass(backend, monkeypatch, dtype, k, regime):
     """L-split scans (ops.lsplit_factor / scan_fwd_launch / scan_bwd_launch): every row cut into k segments that run as rows
     of the same launch -- pass 1 with the `map_only` / `carry_only` kernel modes, composition of the segment maps in each row's
     direction, pass 2 from the true entry states.  Both parameter sets of a BiMamba layer (opposite directions, shared gate):
@@ -510,7 +543,7 @@ def test_scan_lsplit_two_pass_matches_unsplit_and_oracle(backend, monkeypatch, d
     E, SB, L, N, split = 8, 2, 4096, 16, 1
     order = ("u", "delta", "A", "B", "C", "D", "bias")
     act = {"u", "delta", "B", "C"}
-    t1, t2 = _scan_inputs(E, SB, L, N, 31, dev, dtype), _scan_inputs(E, SB, L, N, 32, dev, dtype)
+    t1, t2 = _scan_inputs(E, SB, L, N, 31, dev, dtype, regime), _scan_inputs(E, SB, L, N, 32, dev, dtype, regime)
     dirs = [(0, 1), (1, 0)]
 
     def run(kk):
