@@ -141,6 +141,7 @@ SYMBOLS = {
     "cad_version": (C.c_char_p, []),
     "cad_status_string": (C.c_char_p, [_i]),
     "cad_is_device_build": (_i, []),
+    "cad_debug_set_cu_count": (_i, [_i]),
     "cad_embed_fwd": (_i, [C.POINTER(EmbedArgs), _p]),
     "cad_embed_bwd": (_i, [C.POINTER(EmbedBwdArgs), _p]),
     "cad_embed_bwd_slotted": (_i, [C.POINTER(EmbedBwdArgs), _p, _p]),

@@ -1,4 +1,5 @@
 // Library identification, status strings and the opt-in HIP-event kernel timer behind cad_prof_*.
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -43,7 +44,21 @@ extern "C" const char* cad_status_string(int s) {
 
 int cad_after_launch() { return hipGetLastError() == hipSuccess ? CAD_OK : CAD_ERR_LAUNCH; }
 
+// cad_debug_set_cu_count (test infrastructure): n > 0 replaces the CU count every "one workgroup per CU" launcher sizes its grid with, so
+// that a test can make ONE workgroup walk many blocks / work items at a modest problem size; 0 restores the real value.
+namespace {
+std::atomic<int> g_cu_override{0};
+}
+extern "C" int cad_debug_set_cu_count(int n) {
+    if (n < 0) return CAD_ERR_BAD_ARG;
+    g_cu_override.store(n, std::memory_order_relaxed);
+    return CAD_OK;
+}
+int cad_cu_count_override() { return g_cu_override.load(std::memory_order_relaxed); }
+
 int cad_cu_count() {
+    const int forced = cad_cu_count_override();
+    if (forced > 0) return forced;
 #ifdef CAD_EMU
     return 256;
 #else

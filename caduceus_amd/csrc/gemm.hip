@@ -1154,9 +1154,13 @@ extern "C" int cad_proj_wgrad_only_supported(int M, int K, int64_t T) {
     return M >= 1 && M <= 64 && (K == 256 || K == 512) && T >= GtCfg::NT && (T % GtCfg::NT) == 0 &&
            gt_wgrad_lds(M, K, false) <= 160 * 1024;
 }
+int cad_cu_count_override();  // api.hip: the value set by cad_debug_set_cu_count (tests only), 0 = none
 extern "C" int cad_proj_wx_wgrad_partials(int64_t T) {
     const int64_t nblk = T / GtCfg::NT;
-    return (int)(nblk < 256 ? (nblk < 1 ? 1 : nblk) : 256);
+    int cap = 256;  // (a fixed number, not the CU count: the slot count is part of the summation order)
+    const int forced = cad_cu_count_override();  // tests only: fewer workgroups, several blocks each
+    if (forced > 0 && forced < cap) cap = forced;
+    return (int)(nblk < cap ? (nblk < 1 ? 1 : nblk) : cap);
 }
 #endif
 

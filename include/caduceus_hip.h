@@ -43,6 +43,12 @@ const char* cad_version(void);
 const char* cad_status_string(int status);
 /* 1 when built for the GPU (hipcc, gfx950); 0 for the host-emulator build used only by the test-suite. */
 int cad_is_device_build(void);
+/* TEST INFRASTRUCTURE -- production code never calls it.  The "one workgroup per CU" launchers (cad_proj_*, cad_gemm_stream,
+ * cad_proj_wxT_fp8, ...) size their grids with the CU count of the device, and a workgroup then walks its blocks / work items in a loop:
+ * with n > 0 they take n instead (process-wide, host emulator and device build alike; cad_proj_wx_wgrad_partials follows it below its
+ * own cap of 256), so that a test can make one workgroup walk many blocks at a small problem size.  n = 0 restores the real value.
+ * Results do not depend on it, except the NUMBER of partial slots of cad_proj_wx_wgrad (query cad_proj_wx_wgrad_partials after setting). */
+int cad_debug_set_cu_count(int n);
 
 /* ---------------------------------------------------------------------------------------------------------
  * RCPS / plain embedding gather.   Replaces RCPSEmbedding.forward/.rc (modeling_rcps.py:46-67) and
@@ -367,7 +373,13 @@ int64_t cad_scan_bwd_fold_counter_ints(int64_t SB, int64_t L);
  *                                                                      and d(y) = W_out^T . dout^T of the backward.
  * All operands bf16, row strides ld* in ELEMENTS (multiples of 8); K must satisfy cad_proj_supported(K); any M, T.
  * The per-token result does not depend on the token's position (fixed reduction order): t-frame strands / directions
- * get bit-identical projections. */
+ * get bit-identical projections.
+ * ROUNDING CONTRACT of every 16-bit projection below (bf16 and fp16 alike): the K products of an output element are exact in fp32 and
+ * summed in fp32 (the MFMA accumulators, over all of K and over both panels of cad_proj_xTw), and that fp32 sum is rounded ONCE, to
+ * nearest even, to the output type; a finite sum beyond the output type's range gives +-inf, NaN / inf operands propagate to exactly the
+ * output elements they enter.  fp32 outputs (weight-gradient slots, CAD_GEMM_PARTIALS tiles, cad_gemm_f32) are the fp32 sums themselves.
+ * The two addend forms differ, see cad_proj_wx: thin M / deep K adds the widened addend to the fp32 sum BEFORE the one rounding; thin K
+ * rounds the product first and rounds again after the addition. */
 typedef struct {
     const void* W;
     const void* X;
@@ -396,7 +408,12 @@ int cad_proj_supported(int K);
 /* cad_proj_wx:  out (M, T) = W (M, K) . X (K, T) [+ acc],  all channel-major, thin K (cad_proj_wx_supported: K <= 64,
  * K % 8 == 0, T % 8 == 0) -- dt_proj (K = dt_rank; `dt_proj` inside mamba_inner_fn) and the x_proj input gradient
  * d(xc) = du + W_x^T . d(dbc) of its backward.  X is token-contiguous: the MFMA fragments are transposed on the way out
- * of LDS (ds_read_b64_tr_b16). */
+ * of LDS (ds_read_b64_tr_b16).
+ * Thin-K addend: out = round(round(W . X) + acc) -- the fp32 sums are rounded to the element type (the kernel's staging tile holds 16-bit
+ * values), widened again, added to the widened addend in fp32 and rounded a second time (both to nearest even).  TWO roundings: up to
+ * one output ulp from round(W . X + acc); d(xc) = du + W_x^T . d(dbc) is a gradient at the bf16 class, and the order is fixed, so the
+ * result is deterministic and position-independent.  With act = CAD_ACT_SOFTPLUS_BIAS: out = round(softplus(W . X + bias)), fp32
+ * throughout, one rounding. */
 int cad_proj_wx(const cad_proj_args* a, void* stream);
 int cad_proj_wx_f16(const cad_proj_args* a, void* stream);
 int cad_proj_wx_supported(int K, int64_t T);
