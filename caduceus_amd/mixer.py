@@ -5,25 +5,52 @@ engine.py composes the same computation from per-op autograd Functions (kept for
 readable specification).  Scheduling the backward by hand removes what generic autograd cannot know
 (profiles/r01_step_and_scan_v3_summary.txt: ~40 ms of copies / adds / duplicate GEMMs per 382 ms step):
   * with a tied out_proj, d(y_f) == d(y_r): ONE GEMM, written channel-major directly (no transposing copies);
-  * the scan backward writes dz of parameter set f straight into the dxz buffer and set r's dz is added in place;
-  * weight gradients (reductions over all T tokens with tiny outputs) run as strided-batch GEMMs over 64 K-chunks plus an
-    fp32 sum, 3-5x faster than the un-split library GEMM;
+  * the two scans share the gate z and the upstream gradient: set f's backward kernel writes the gate gradient of both straight into
+    the dxz buffer (cad_scan_bwd_args.out2);
+  * weight gradients (reductions over all T tokens with tiny outputs) are fp32 partial tiles of the own kernels, summed by one fold
+    launch at the end of the backward;
   * the conv forward / backward of both parameter sets run as one launch each (x read once, dx = dx_f + dx_r written once); dB/dC partial sums are reduced straight into the rows of
     the x_proj gradient operand; du is folded into the x_proj backward GEMM (addmm).
-All kernels are the C-ABI entry points of include/caduceus_hip.h.  Projections: in_proj, x_proj, dt_proj (+ bias + softplus), d(y),
-d(dt_lr) + dW_dt (one pass, cad_proj_wx_wgrad) and the x_proj input gradient run on the library's own MFMA kernels (csrc/gemm.hip,
-gemm_fp8.hip); out_proj forward, d(x2d) and the three remaining weight gradients are hipBLASLt through torch.
+BiMambaMixerFn.forward / backward read as the schedule; every step of it is one module-level stage function (_in_proj ... _dW_in_partials)
+that owns its dispatch chain: the own kernel if it serves the shape, else the next kernel, else the GEMM library through torch.
+All kernels are the C-ABI entry points of include/caduceus_hip.h.  At the benchmarked shapes (bf16, d_model 256 / 512) EVERY product runs
+on the library's own MFMA kernels (csrc/gemm.hip, gemm_fp8.hip): in_proj, x_proj, dt_proj (+ bias + softplus), out_proj, d(y), d(dt_lr) +
+dW_dt (one pass, cad_proj_wx_wgrad), dW_x, d(xc), d(x2d), dW_in and dW_out; fp32 takes cad_gemm_f32, and only bf16 / fp16 shapes that no
+own kernel serves reach hipBLASLt through torch.
 Scan launches with fewer workgroups than the GPU has CUs are L-split (ops.lsplit_factor).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import torch
 
 from . import _lib as L
 from . import ops
+
+# the seven parameters of one parameter set (f, r), in the order BiMambaMixerFn.apply takes them
+SetParams = namedtuple("SetParams", "conv_w conv_b W_x W_dt dt_bias A_log D")
+# what one parameter set saves for the backward (fp32: A = -exp(A_log), D, dt_bias, conv_w (E, K), conv_b; compute dtype: the rest)
+SetSaved = namedtuple("SetSaved", "xc delta A dbc D dt_bias conv_w conv_b w_x w_dt state A_log")
+# outputs of one set's scan backward: dBC = the (2, npart, N, SB, L) partial slots of dB / dC; dA, dD, dbias are accumulated (zeroed)
+SetWork = namedtuple("SetWork", "du ddelta dA dD dbias dBC npart")
+# the non-tensor context of a backward: pdtypes = SetParams of dtypes (None: no such parameter) per set, delta_is_dt per set
+Meta = namedtuple("Meta", "SB Lq split pdtypes conv_w_shapes win_dt wout_dt delta_is_dt k")
+# prepare_step_cache's per-layer record: compute-dtype weights and their transposes (w_x, w_dt, A and their transposes: one per set)
+StepCache = namedtuple("StepCache", "versions w_in w_out w_x w_dt A w_inT w_outT w_xT w_dtT w_out2 w_in_fp8")
+_DIRS = ((0, 1), (1, 0))  # (rev_lo, rev_hi) of set f and set r: which of the two strand row groups a set scans reversed
+
+
+def _flatten(records):
+    return [t for r in records for t in r]
+
+
+def _unflatten(cls, flat, n):
+    """The inverse of _flatten for n records of namedtuple cls at the head of flat -> (records, what follows them)."""
+    w = len(cls._fields)
+    return [cls(*flat[j * w:(j + 1) * w]) for j in range(n)], flat[n * w:]
 
 
 def _conv_fwd2(x, params, split, dirs):
@@ -42,15 +69,15 @@ def _conv_fwd2(x, params, split, dirs):
     return outs
 
 
-def _zeros_f32(shapes, device):
-    """fp32 zero tensors of the given shapes carved out of ONE allocation (one fill kernel instead of one per tensor:
-    the accumulated per-channel gradients of a layer are ten tiny tensors)."""
-    sizes = [int(torch.Size(s).numel()) for s in shapes]
+def _zeros_f32(spec, device):
+    """{name: zero tensor} for spec = {name: (shape, torch.float32 | torch.int32)}, carved out of ONE fp32 allocation (one fill kernel
+    instead of one per tensor: the accumulated per-channel gradients of a layer are ten tiny tensors; zero bits are zero counters)."""
+    sizes = [int(torch.Size(s).numel()) for s, _ in spec.values()]
     offs = [0]
     for n in sizes:
         offs.append(offs[-1] + (n + 3) // 4 * 4)  # 16-byte aligned views
     flat = torch.zeros((offs[-1],), dtype=torch.float32, device=device)
-    return [flat[o:o + n].view(s) for o, n, s in zip(offs, sizes, shapes)]
+    return {name: flat[o:o + n].view(dt).view(s) for o, n, (name, (s, dt)) in zip(offs, sizes, spec.items())}
 
 
 def _conv_bwd2(x, params, douts, dx, split, dirs, bufs=None):
@@ -124,7 +151,7 @@ def _own_wgrad_chunked(X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
 def _wgrad_cm_tm(a_cm: torch.Tensor, b_tm: torch.Tensor) -> torch.Tensor:
     """a (M, T) channel-major @ b (T, N) token-major -> (M, N) fp32."""
     M, T = a_cm.shape
-    if _OWN_GEMM and (b_tm.shape[1] <= 256 or _OWN_GEMM_D512):  # (one column tile: at d_model 512 the library's K-split was 12 % faster, profiles/r04_gemm_stream.txt)
+    if _OWN_GEMM:
         own = ops.wgrad_cm_tm(a_cm, b_tm)
         if own is not None:
             return own
@@ -137,33 +164,27 @@ def _wgrad_cm_tm(a_cm: torch.Tensor, b_tm: torch.Tensor) -> torch.Tensor:
     return torch.sum(ops.bmm(a_cm.view(M, n, Kc).permute(1, 0, 2), b_tm.view(n, Kc, -1)), dim=0, dtype=torch.float32)
 
 
-# The two scans of a BiMamba layer share the gate z and the upstream gradient: set 0's backward kernel evaluates the gate
-# gradient of both (cad_scan_bwd_args.out2).  CADUCEUS_AMD_SHARED_GATE=0 keeps one dz per set + an add (A/B switch).
-_SHARED_GATE = os.environ.get("CADUCEUS_AMD_SHARED_GATE", "1") != "0"
-# delta_bias + softplus in the epilogue of the dt_proj kernel (HBM-bound, idle VALU) instead of the scan prologues
-_FUSED_SOFTPLUS = os.environ.get("CADUCEUS_AMD_FUSED_SOFTPLUS", "1") != "0"
-
-
-# d(dt_lr) and dW_dt from one pass over d(delta) (cad_proj_wx_wgrad); CADUCEUS_AMD_FUSED_WGRAD=0 keeps the two-kernel path (A/B switch)
-_FUSED_WGRAD = os.environ.get("CADUCEUS_AMD_FUSED_WGRAD", "1") != "0"
+# Test and A/B handles, not options: tests/test_proj.py, tests/test_fold_stream.py and tools/layer_bench.py --ab set them in-process to
+# reach the branch behind the own kernel (the real path of shapes the own kernels refuse); only the defaults run on the device.
+# d(dt_lr) and dW_dt from one pass over d(delta) (cad_proj_wx_wgrad); False: the two-kernel path
+_FUSED_WGRAD = True
 # dW_x = d(dbc) . xc^T on the weight-gradient stage of the same kernel (W == NULL) instead of the GEMM library + a partial sum
-_OWN_DWX = os.environ.get("CADUCEUS_AMD_OWN_DWX", "1") != "0"
-# out_proj forward on the own token-major-output MFMA kernel (cad_proj_xTw); CADUCEUS_AMD_OWN_OUT_PROJ=0: hipBLASLt on [y_f ; y_r]
-_OWN_OUT_PROJ = os.environ.get("CADUCEUS_AMD_OWN_OUT_PROJ", "1") != "0"
+_OWN_DWX = True
+# out_proj forward on the own token-major-output MFMA kernel (cad_proj_xTw); False: hipBLASLt on [y_f ; y_r]
+_OWN_OUT_PROJ = True
 # d(x2d), dW_in and dW_out -- the products whose two operands both stream -- on the own tiled MFMA kernel (cad_gemm_stream: fp32
-# accumulation over ALL tokens for the weight gradients); CADUCEUS_AMD_OWN_GEMM=0: torch.mm / K-split bmm (hipBLASLt)
-_OWN_GEMM = os.environ.get("CADUCEUS_AMD_OWN_GEMM", "1") != "0"
-# ... also at d_model 512 (configs[4]: two 256-column tiles, the strided operand is walked twice).  The library products are 0.5 ms per
-# layer faster there (31.75 vs 32.28 ms per layer, 535.2 vs 538.2 ms per step: profiles/r05_gemm_stream_d512.txt), i.e. 0.6 % of a step
-# is the price of a configs[4] step without a library GEMM and with fp32-accumulated weight gradients; CADUCEUS_AMD_OWN_GEMM_D512=0
-# takes torch.mm / the K-split bmm for these three products at d_model > 256
-_OWN_GEMM_D512 = os.environ.get("CADUCEUS_AMD_OWN_GEMM_D512", "1") != "0"
-# in_proj and d(y) at d_model 512 on the same tiled kernel (cad_gemm_stream, column tiles fastest) instead of the W-stationary cad_proj_wxT,
-# which streams the token operand once per 128-row block of W (16 times at M = 2048); CADUCEUS_AMD_STREAM_PROJ_D512=0: cad_proj_wxT
-_STREAM_PROJ_D512 = os.environ.get("CADUCEUS_AMD_STREAM_PROJ_D512", "1") != "0"
-# A/B switch: out_proj and x_proj at d_model 512 as plain torch products (hipBLASLt) instead of cad_gemm_stream / the two K halves of
-# cad_proj_wx -- the library is ~1.3 % of the configs[4] step faster on these two (profiles/r05_step_trace_c4.txt); default: own kernels
-_LIB_OUT_X_D512 = os.environ.get("CADUCEUS_AMD_LIB_OUT_X_PROJ_D512", "0") == "1"
+# accumulation over ALL tokens for the weight gradients); False: torch.mm / K-split bmm (hipBLASLt).  At d_model 512 (configs[4]: two
+# 256-column tiles, the strided operand is walked twice) the library products are 0.5 ms per layer faster (31.75 vs 32.28 ms per layer,
+# 535.2 vs 538.2 ms per step: profiles/r05_gemm_stream_d512.txt), i.e. 0.6 % of a step is the price of a configs[4] step without a
+# library GEMM and with fp32-accumulated weight gradients
+_OWN_GEMM = True
+# in_proj, out_proj and d(y) at d_model 512 on the same tiled kernel (cad_gemm_stream, column tiles fastest) instead of the W-stationary
+# cad_proj_wxT, which streams the token operand once per 128-row block of W (16 times at M = 2048); False: cad_proj_wxT / the library
+_STREAM_PROJ_D512 = True
+# the fp32 partial tiles of a layer's weight gradients (dW_in, dW_out: K slices of cad_gemm_stream; dW_x, dW_dt: per-workgroup slots of
+# cad_proj_wx_wgrad) summed by ONE own launch at the end of the backward (cad_fold_f32_multi) instead of four torch reductions + an add;
+# False: torch.sum per tensor
+_GLUE_FOLD = True
 # BASELINE configs[4]: in_proj on the fp8 (OCP e4m3) matrix cores (csrc/gemm_fp8.hip); set CADUCEUS_AMD_FP8_PROJ=1 or call
 # set_fp8_in_proj(True).  Forward only: the backward keeps the bf16 activations it saves today.
 _FP8_IN_PROJ = os.environ.get("CADUCEUS_AMD_FP8_PROJ", "0") == "1"
@@ -171,11 +192,7 @@ _FP8_IN_PROJ = os.environ.get("CADUCEUS_AMD_FP8_PROJ", "0") == "1"
 # issue, the fold by memory latency: 0.39 ms per layer of fold kernel leave the critical path); CADUCEUS_AMD_STREAM_FOLD=0: the fold
 # kernel behind the scan (cad_reduce_partials_multi) -- same summation order, bit-identical gradients
 _STREAM_FOLD = os.environ.get("CADUCEUS_AMD_STREAM_FOLD", "1") != "0"
-_STREAM_FOLD_MIN_CHUNKS = 16  # rows shorter than this many 512-position chunks keep the fold kernel behind the scan (see backward)
-# the fp32 partial tiles of a layer's weight gradients (dW_in, dW_out: K slices of cad_gemm_stream; dW_x, dW_dt: per-workgroup slots of
-# cad_proj_wx_wgrad) summed by ONE own launch at the end of the backward (cad_fold_f32_multi) instead of four torch reductions + an add;
-# CADUCEUS_AMD_GLUE_FOLD=0: torch.sum per tensor
-_GLUE_FOLD = os.environ.get("CADUCEUS_AMD_GLUE_FOLD", "1") != "0"
+_STREAM_FOLD_MIN_CHUNKS = 16  # rows shorter than this many 512-position chunks keep the fold kernel behind the scan (see _scan_bwd)
 
 
 # test hook (tests/test_configs.py): a list here receives, per backward call, the operands of the x_proj weight gradient of both
@@ -196,7 +213,7 @@ def prepare_step_cache(pairs, act: torch.dtype) -> None:
     """Compute-dtype copies of every layer's projection weights and A = -exp(A_log), for ALL layers at once with
     multi-tensor (foreach) launches -- instead of ten tiny cast / exp / neg kernels per layer per step
     (profiles/r02_step_trace.txt: ~1000 sub-5-us launches per step).  pairs: [(mamba_fwd, mamba_rev)] of the layers that run
-    BiMambaMixerFn.  The copies are attached to mamba_fwd together with the parameter versions they were made from;
+    BiMambaMixerFn.  The copies are attached to mamba_fwd (a StepCache) together with the parameter versions they were made from;
     BiMambaMixerFn.forward uses them only while those versions are current."""
     if not pairs:
         return
@@ -222,18 +239,17 @@ def prepare_step_cache(pairs, act: torch.dtype) -> None:
             return v
         return torch.empty(p.shape, dtype=act, device=p.device)
 
+    order = ("in", "out", "x", "dt", "x", "dt")  # w_in, w_out, w_x_f, w_dt_f, w_x_r, w_dt_r: the order the stacked buffers are filled in
     for (mf, mr), pl in zip(pairs, plist):
         ps = [pl["in"][0], pl["out"][0], pl["x"][0], pl["dt"][0], pl["x"][1], pl["dt"][1]]
-        out = [alloc(kd, p) for kd, p in zip(("in", "out", "x", "dt", "x", "dt"), ps)]
+        out = [alloc(kd, p) for kd, p in zip(order, ps)]
         src += [p.detach() for p in ps]
         dst += out
         alog += [mf.A_log.detach().float(), mr.A_log.detach().float()]
         owners.append((mf, ps + [mf.A_log, mr.A_log], out))
     torch._foreach_copy_(dst, src)
-    # (W_in^T feeds cad_gemm_stream: d(x2d) -- d_model <= 256, or 512 with the own tiled GEMM on -- and the streamed in_proj forward at
-    # d_model 512, which must not depend on the d(x2d) switches: ADVICE r5)
-    need_in_T = "in" in stacked and ((_OWN_GEMM and (stacked["in"].shape[2] <= 256 or _OWN_GEMM_D512)) or
-                                     (_STREAM_PROJ_D512 and stacked["in"].shape[2] > 256))
+    # (W_in^T is prepared when one of its two consumers -- the streamed in_proj, d(x2d) -- will ask for it)
+    need_in_T = "in" in stacked and (_dx2d_is_streamed() or _in_proj_is_streamed(stacked["in"].shape[2], act))
     trans = {kd: stacked[kd].transpose(1, 2).contiguous() for kd in ("out", "x", "dt") + (("in",) if need_in_T else ()) if kd in stacked}
     cursor = {kd: 0 for kd in kinds}
 
@@ -244,28 +260,314 @@ def prepare_step_cache(pairs, act: torch.dtype) -> None:
             return v
         return w.t().contiguous()
 
-    for mf, ps, out in owners:
-        # [W_out^T, W_x_f^T, W_dt_f^T, W_x_r^T, W_dt_r^T, W_in^T], in the order the stacked buffers were filled
-        out.append([transposed(kd, out[j]) for kd, j in (("out", 1), ("x", 2), ("dt", 3), ("x", 4), ("dt", 5))] +
-                   [transposed("in", out[0]) if need_in_T else None])
+    wTs = []
+    for mf, ps, (w_in, w_out, w_x_f, w_dt_f, w_x_r, w_dt_r) in owners:  # (transposes in the order of the stacked buffers, W_in^T last)
+        w_outT, w_x_fT, w_dt_fT, w_x_rT, w_dt_rT = [transposed(kd, w) for kd, w in zip(order[1:], (w_out, w_x_f, w_dt_f, w_x_r, w_dt_r))]
+        wTs.append(dict(w_outT=w_outT, w_xT=(w_x_fT, w_x_rT), w_dtT=(w_dt_fT, w_dt_rT), w_inT=transposed("in", w_in) if need_in_T else None))
     negA = torch._foreach_exp(alog)
     torch._foreach_neg_(negA)
-    for i, (mf, ps, out) in enumerate(owners):
-        tr = out.pop()  # [W_out^T, W_x_f^T, W_dt_f^T, W_x_r^T, W_dt_r^T, W_in^T]
-        mf._cad_step_cache = {"versions": [(id(p), p._version) for p in ps], "w": out, "A": (negA[2 * i], negA[2 * i + 1]),
-                              "wT": {"out": tr[0], "x": (tr[1], tr[3]), "dt": (tr[2], tr[4]), "in": tr[5]}}
-        if _STREAM_PROJ_D512 and not _LIB_OUT_X_D512 and out[1].shape[0] > 256:
-            # d_model 512: out_proj streams [y_f ; y_r] against [W_out, W_out] (K = 2 E) -- built once per step, not per layer call
-            mf._cad_step_cache["w_out2"] = torch.cat([out[1], out[1]], 1)
-        if _FP8_IN_PROJ and act == torch.bfloat16 and ops.fp8_proj_supported(out[0], out[0].shape[1]):
-            mf._cad_step_cache["w_in_fp8"] = ops.quant_weight_fp8(ps[0])  # from the fp32 master weight, once per step
+    for (mf, ps, (w_in, w_out, w_x_f, w_dt_f, w_x_r, w_dt_r)), wT, A_f, A_r in zip(owners, wTs, negA[0::2], negA[1::2]):
+        # d_model 512: out_proj streams [y_f ; y_r] against [W_out, W_out] (K = 2 E) -- built once per step, not per layer call
+        w_out2 = torch.cat([w_out, w_out], 1) if _out_proj_is_streamed(w_out.shape[0]) else None
+        w_in_fp8 = None
+        if _FP8_IN_PROJ and act == torch.bfloat16 and ops.fp8_proj_supported(w_in, w_in.shape[1]):
+            w_in_fp8 = ops.quant_weight_fp8(mf.in_proj.weight)  # from the fp32 master weight, once per step
+        mf._cad_step_cache = StepCache(versions=[(id(p), p._version) for p in ps], w_in=w_in, w_out=w_out, w_x=(w_x_f, w_x_r),
+                                       w_dt=(w_dt_f, w_dt_r), A=(A_f, A_r), w_out2=w_out2, w_in_fp8=w_in_fp8, **wT)
 
 
 def _cached(mf, params):
     c = getattr(mf, "_cad_step_cache", None)
-    if c is None or c["versions"] != [(id(p), p._version) for p in params]:
+    if c is None or c.versions != [(id(p), p._version) for p in params]:
         return None
     return c
+
+
+def _transposed(cache, field, w, i=None):
+    """W^T from the step cache (field of StepCache, set i of a per-set field), or -- no step cache (eval, or the parameters changed
+    since prepare_step_cache), or a transpose it did not prepare -- made here."""
+    wT = None if cache is None else getattr(cache, field)
+    if wT is not None and i is not None:
+        wT = wT[i]
+    return w.t().contiguous() if wT is None else wT
+
+
+# ---- forward stages --------------------------------------------------------------------------------------------------------------
+def _in_proj_is_streamed(Dm: int, act) -> bool:  # d_model 512: both operands streamed through the tiled kernel, which takes W_in^T
+    return _STREAM_PROJ_D512 and Dm > 256 and act == torch.bfloat16
+
+
+def _in_proj(x2d, W_in, w_in, cache, fp8_act):
+    """xz (2E, T) channel-major = W_in x2d^T."""
+    T, Dm = x2d.shape
+    if _FP8_IN_PROJ and x2d.dtype == torch.bfloat16 and ops.fp8_proj_supported(x2d, Dm):
+        # fp8 matrix cores: per-token e4m3 activations x per-row e4m3 weights, fp32 accumulation, bf16 channel-major output
+        wq, sw = cache.w_in_fp8 if (cache and cache.w_in_fp8 is not None) else ops.quant_weight_fp8(W_in)
+        # e4m3 activations + per-token scales: written by the add + norm kernel that produced x2d (fp8_act), else quantised here
+        xq, sx = (fp8_act[0].view(T, Dm), fp8_act[1]) if fp8_act is not None else ops.quant_rows_fp8(x2d)
+        return ops.proj_wxT_fp8(wq, sw, xq, sx)
+    xz = None
+    if _in_proj_is_streamed(Dm, x2d.dtype):
+        # A = tokens, B = W_in^T, channel-major result (None if the shape is not served)
+        xz = ops.gemm_out_t(x2d, _transposed(cache, "w_inT", w_in))
+    if xz is None and ops.proj_supported(x2d, Dm):  # bf16: the W-stationary MFMA kernel (csrc/gemm.hip) writes channel-major directly
+        xz = ops.proj_wxT(w_in, x2d)
+    if xz is None:
+        xz = ops.mm(w_in, x2d.t())  # fp32: cad_gemm_f32; a bf16 shape no own kernel serves: the library
+    return xz
+
+
+def _x_proj(w_x, xc):
+    """[dt_lr ; B ; C] (R + 2N, T) = W_x xc, xc (E, T) channel-major."""
+    (M, E), T = w_x.shape, xc.shape[1]
+    if ops.proj_wx_supported(xc, E, T, M=M):  # thin-M / deep-K MFMA kernel: xc read once, W_x in LDS
+        return ops.proj_wx(w_x, xc)
+    if E % 128 == 0 and ops.proj_wx_supported(xc, E // 2, T, M=M):
+        # d_inner 1024 (configs[4]): 64 rows x 1024 of W_x do not fit LDS next to the X ring -- two K halves.  The first half is
+        # STORED in bf16 and widened again as the addend of the second, so dt_lr / B / C see two roundings (first half, then the
+        # sum), not one fp32 accumulation over K; xc is still read once
+        dbc = ops.proj_wx(w_x[:, :E // 2], xc[:E // 2])
+        return ops.proj_wx(w_x[:, E // 2:], xc[E // 2:], out=dbc, acc=dbc)
+    return ops.mm(w_x, xc)
+
+
+def _dt_proj(w_dt, dt_lr, dt_bias):
+    """(delta (E, T), delta_is_dt): delta = softplus(W_dt dt_lr + dt_bias) from the own kernel, which the scans then take as it is
+    (delta_is_dt) -- delta_bias + softplus in the epilogue of an HBM-bound kernel with idle VALU instead of the scan prologues; from the
+    library plain W_dt dt_lr, and the scans add the bias and apply the softplus."""
+    R, T = dt_lr.shape
+    if ops.proj_wx_supported(dt_lr, R, T):  # thin-K MFMA kernel (transposing LDS reads), csrc/gemm.hip
+        return ops.proj_wx(w_dt, dt_lr, softplus_bias=dt_bias), True
+    return ops.mm(w_dt, dt_lr), False
+
+
+def _scan_fwd(sets, z, ycat, delta_is_dt, split, k):
+    """Both parameter sets in one scan launch, y of set i into rows [i E, (i + 1) E) of ycat; k > 1: every row cut into k segments along
+    L (ops.lsplit_factor) when the launch would otherwise leave CUs idle (Caduceus-Ph at batch 1).  Returns (sets with their chunk
+    states, the segments' decay products the backward needs again)."""
+    lib = L.get_lib()
+    E, SB, Lq = z.shape
+    args = (L.ScanArgs * 2)()
+    with_state = []
+    for i, (s, out) in enumerate(zip(sets, ycat.view(2, E, SB, Lq))):
+        N = s.A.shape[1]
+        R = s.dbc.shape[0] - 2 * N
+        state = torch.empty((lib.cad_scan_state_floats(E, SB * k, Lq // k, N),), dtype=torch.float32, device=z.device)
+        Bm, Cm = s.dbc[R:R + N], s.dbc[R + N:]
+        stream = L.stream_and_check(s.xc, s.delta, s.A, Bm, Cm, s.D, z, s.dt_bias, out, state)
+        args[i] = L.ScanArgs(L.ptr(s.xc), L.ptr(s.delta), L.ptr(s.A), L.ptr(Bm), L.ptr(Cm), L.ptr(s.D), L.ptr(z), L.ptr(s.dt_bias),
+                             L.ptr(out), L.ptr(state), SB * k, Lq // k, split * k, E, N, *_DIRS[i], L.dtype_code(z.dtype))
+        args[i].delta_is_dt = int(delta_is_dt[i])
+        with_state.append(s._replace(state=state))
+    _keep, seg_P = ops.scan_fwd_launch(lib, args, 2, stream, k, [s.A for s in sets], _DIRS, split)
+    return with_state, seg_P
+
+
+def _out_proj_is_streamed(Dm: int) -> bool:  # d_model 512: W_out is too deep for cad_proj_xTw's resident fragments
+    return _STREAM_PROJ_D512 and Dm > 256
+
+
+def _out_proj(w_out, ycat, cache):
+    """out (T, D) token-major = W_out (y_f + y_r), ycat = [y_f ; y_r] (2E, T): the out_proj is tied."""
+    Dm, E = w_out.shape
+    T = ycat.shape[1]
+    if _OWN_OUT_PROJ and ops.proj_xTw_supported(ycat, Dm, E, T):
+        # both panels through one set of resident W_out fragments, token-major output (cad_proj_xTw)
+        return ops.proj_xTw(w_out, ycat[:E], ycat[E:])
+    # both operands streamed (cad_gemm_stream), [y_f ; y_r] against [W_out, W_out] with K = 2 E; plain products for anything the kernel
+    # does not serve
+    out2d = None
+    if _STREAM_PROJ_D512 and ycat.dtype == torch.bfloat16:
+        w_out2 = cache.w_out2 if cache else None
+        out2d = ops.proj_xTw_stream(w_out2 if w_out2 is not None else torch.cat([w_out, w_out], 1), ycat)
+    if out2d is None:
+        out2d = ops.mm(ycat.t(), torch.cat([w_out, w_out], 1).t())
+    return out2d
+
+
+# ---- backward stages -------------------------------------------------------------------------------------------------------------
+def _d_y(dout2d, w_out, cache):
+    """d(y_f) == d(y_r) (E, T) channel-major = W_out^T dout^T: with a tied out_proj the two are the same tensor."""
+    Dm = dout2d.shape[1]
+    dy = None
+    if _STREAM_PROJ_D512 and Dm > 256 and dout2d.dtype == torch.bfloat16:
+        dy = ops.gemm_out_t(dout2d, w_out)  # (T, D) @ W_out (D, E) -> (E, T): the weight as it lies is the row-major B operand
+    if dy is None and ops.proj_supported(dout2d, Dm):
+        dy = ops.proj_wxT(_transposed(cache, "w_outT", w_out), dout2d)
+    if dy is None:
+        dy = ops.mm(w_out.t(), dout2d.t())
+    return dy
+
+
+def _dW_out(ycat, dout2d, glue):
+    """dW_out (D, E) fp32 from [y_f ; y_r] (2E, T): both halves multiply the same tied weight."""
+    E, Dm = ycat.shape[0] // 2, dout2d.shape[1]
+    part = ops.wgrad_cm_tm(ycat, dout2d, return_partials=True) if (_GLUE_FOLD and _OWN_GEMM) else None  # (slices, 2E, D)
+    if part is None:
+        dW_cat = _wgrad_cm_tm(ycat, dout2d)
+        return (dW_cat[:E] + dW_cat[E:]).t()
+    # the fold adds the two halves (second level) as it sums the slices
+    dW_out_ED = torch.empty((E, Dm), dtype=torch.float32, device=ycat.device)
+    glue.append((part, dW_out_ED, E * Dm, part.shape[0], 2 * E * Dm, 2, E * Dm))
+    return dW_out_ED.t()
+
+
+def _scan_bwd(sets, xz, ycat, dy, seg_P, meta):
+    """The scan backward of both sets in one launch, the fold of its dB / dC partial slots into rows [R:] of each set's x_proj gradient
+    operand, and the exact gate gradient at lost gates.  Returns (dxz with its [dz] half written, per-set SetWork, per-set d(dbc)
+    with rows [R:] written, the zeroed conv dw / db buffers per set)."""
+    lib = L.get_lib()
+    SB, Lq, split, k, act, dev = meta.SB, meta.Lq, meta.split, meta.k, xz.dtype, xz.device
+    E = xz.shape[0] // 2
+    z = xz[E:]
+    dxz = torch.empty_like(xz)  # [dx ; dz]: the gate z is shared, set f's kernel writes the gradient of both gates (out2 = y_r)
+    spec = {}
+    for i, s in enumerate(sets):  # per set: dA, dD, ddelta_bias (scan), dw, db (conv): accumulated by the kernels -> zeroed
+        spec.update({("dA", i): (s.A.shape, torch.float32), ("dD", i): (s.D.shape, torch.float32),
+                     ("dbias", i): (s.dt_bias.shape, torch.float32), ("conv_dw", i): (s.conv_w.shape, torch.float32),
+                     ("conv_db", i): (s.conv_b.shape if s.conv_b is not None else (0,), torch.float32)})
+    spec.update({("fix_cnt", i): ((1,), torch.int32) for i in range(2)})  # worklist counters of the exact z == 0 gate gradient
+    N = sets[0].A.shape[1]
+    npart = lib.cad_scan_bwd_partials(E)
+    nch = max(1, (Lq // k) // int(lib.cad_scan_bwd_chunk_len()))
+    # (the fold follows the scan chunk by chunk with one workgroup per CU: it pays for long rows -- many chunks per (row, slice) item,
+    # few items per workgroup; short rows in large batches (configs[1]: 2 chunks, 64 items per workgroup) keep the streaming fold
+    # kernel behind the scan: 4.18 vs 4.83 ms per layer, profiles/r06_ab_stream_fold.txt)
+    stream_fold = (_STREAM_FOLD and sets[1].A.shape[1] == N and ops.fold_stream_supported(N, npart, Lq // k, act)
+                   and nch >= _STREAM_FOLD_MIN_CHUNKS and npart * SB * k * 2 <= 4 * ops._cu_count()
+                   and ops.fold_side_available(dev))
+    if stream_fold:  # arrival counters (set, row, chunk) and give-up records (set, row, slice) of the concurrent fold
+        nci = (int(lib.cad_scan_bwd_fold_counter_ints(SB * k, Lq // k)) + 3) // 4 * 4  # chunk arrivals + started count + CU marks
+        spec.update({"fold_counters": ((2, nci), torch.int32), "give_ups": ((2, SB * k, npart), torch.int32)})
+    zero = _zeros_f32(spec, dev)
+    n_fix = lib.cad_scan_gate_fix_entries(E, SB, Lq)
+    fix_list = [torch.empty((n_fix,), dtype=torch.int64, device=dev) for _ in range(2)]
+    args = (L.ScanBwdArgs * 2)()
+    work = []
+    for i, (s, y) in enumerate(zip(sets, ycat.view(2, E, SB, Lq))):
+        N = s.A.shape[1]
+        R = s.dbc.shape[0] - 2 * N
+        np_i = lib.cad_scan_bwd_partials(E)
+        w = SetWork(torch.empty_like(s.xc), torch.empty_like(s.xc), zero["dA", i], zero["dD", i], zero["dbias", i],
+                    torch.empty((2, np_i, N, SB, Lq), dtype=ops.scan_slot_dtype(act), device=dev), np_i)
+        dz = dxz[E:] if i == 0 else None
+        Bm, Cm = s.dbc[R:R + N], s.dbc[R + N:]
+        stream = L.stream_and_check(s.xc, s.delta, s.A, Bm, Cm, s.D, z, s.dt_bias, dy, s.state, w.du, w.ddelta, dz, w.dA, w.dBC, w.dD,
+                                    w.dbias)
+        args[i] = L.ScanBwdArgs(L.ptr(s.xc), L.ptr(s.delta), L.ptr(s.A), L.ptr(Bm), L.ptr(Cm), L.ptr(s.D), L.ptr(z), L.ptr(s.dt_bias),
+                                L.ptr(dy), L.ptr(y), L.ptr(s.state), L.ptr(w.du), L.ptr(w.ddelta), L.ptr(dz), L.ptr(w.dA),
+                                *map(L.ptr, w.dBC), L.ptr(w.dD), L.ptr(w.dbias), SB * k, Lq // k, split * k, E, N, *_DIRS[i],
+                                L.dtype_code(act), w.npart, None, None, L.ptr(ycat[E:]) if i == 0 else None, L.ptr(fix_list[i]),
+                                L.ptr(zero["fix_cnt", i]), L.ptr(dxz[E:]))
+        args[i].delta_is_dt = int(meta.delta_is_dt[i])
+        if stream_fold:
+            args[i].fold_counters = L.ptr(zero["fold_counters"][i])
+        work.append(w)
+    ddbcs = [torch.empty_like(s.dbc) for s in sets]
+    rows = []  # per set: (dB slots, dC slots, dB rows of d(dbc), dC rows of d(dbc))
+    for s, w, ddbc in zip(sets, work, ddbcs):
+        N = s.A.shape[1]
+        R = s.dbc.shape[0] - 2 * N
+        rows.append((*map(L.ptr, w.dBC), L.ptr(ddbc[R:R + N]), L.ptr(ddbc[R + N:])))
+    launch_scan = lambda: ops.scan_bwd_launch(lib, args, 2, stream, k, seg_P, _DIRS, split)
+    if stream_fold:
+        # ... chunk by chunk on a second stream while the scan still runs (cad_fold_partials_stream): the side stream follows the scan launch
+        fargs = (L.FoldArgs * 2)()
+        for i, (s, w) in enumerate(zip(sets, work)):
+            fargs[i] = L.FoldArgs(*rows[i], L.ptr(zero["fold_counters"][i]), L.ptr(zero["give_ups"][i]), SB * k, Lq // k, split * k,
+                                  s.A.shape[1], w.npart, *_DIRS[i], L.dtype_code(act))
+        _keep = ops.fold_behind_scan(lib, fargs, 2, dev, launch_scan, give_ups=zero["give_ups"])
+    else:
+        _keep = launch_scan()
+    # the gate fix runs behind the scan: a no-op unless some gate is lost (z == 0; fp16: |z| <= 2^-15)
+    L.check(lib.cad_scan_bwd_gate_fix(args, 2, stream), "cad_scan_bwd_gate_fix")
+    if not stream_fold:
+        # ... by one launch behind the scan (four folds: cad_reduce_partials_multi)
+        jobs = (L.ReduceJob * 4)(*[L.ReduceJob(src, dst) for dB_s, dC_s, dB, dC in rows for src, dst in ((dB_s, dB), (dC_s, dC))])
+        assert work[0].npart == work[1].npart and sets[0].A.shape[1] == sets[1].A.shape[1], "one fold launch: both sets share depth and d_state"
+        L.check(lib.cad_reduce_partials_multi(jobs, 4, work[0].npart, sets[0].A.shape[1] * SB * Lq, L.dtype_code(act), stream),
+                "cad_reduce_partials_multi")
+    return dxz, work, ddbcs, [(zero["conv_dw", i], zero["conv_db", i] if s.conv_b is not None else None) for i, s in enumerate(sets)]
+
+
+def _d_dt_lr(s, w, ddbc, i, cache, slots):
+    """d(dt_lr) = W_dt^T d(delta) into rows [:R] of d(dbc) (rows [R:] hold the folded dB / dC: the gradient of [dt_lr ; B ; C] is
+    assembled in place), and dW_dt (E, R) fp32 -- or None: left in slots["dt"][i] for the fold of the weight-gradient partials."""
+    (E, T), R = s.xc.shape, s.w_dt.shape[1]
+    ddelta, dt_lr, out = w.ddelta, s.dbc[:R], ddbc[:R]
+    if _FUSED_WGRAD and ops.proj_wx_wgrad_supported(ddelta, R, E, T):
+        # d(dt_lr) and dW_dt = d(delta) dt_lr^T from ONE pass over d(delta) (cad_proj_wx_wgrad)
+        if "dt" not in slots:
+            slots["dt"] = ops.wgrad_partials(T, E, R, ddelta.device, nsets=2)
+        ops.proj_wx_wgrad(_transposed(cache, "w_dtT", s.w_dt, i), ddelta, dt_lr, out=out, part=slots["dt"][i])
+        return None
+    if ops.proj_wx_supported(ddelta, E, T, M=R):
+        ops.proj_wx(_transposed(cache, "w_dtT", s.w_dt, i), ddelta, out=out)
+    else:
+        ops.mm(s.w_dt.t(), ddelta, out=out)
+    if _OWN_DWX and _own_wgrad_chunked_ok(ddelta, R):
+        return _own_wgrad_chunked(ddelta, dt_lr).t()
+    return _wgrad_cm_cm(ddelta, dt_lr)
+
+
+def _dW_x(s, ddbc, i, slots):
+    """dW_x (R + 2N, E) fp32 = d(dbc) xc^T -- or None: left in slots["x"][i] for the fold of the weight-gradient partials."""
+    xc, (E, T), M = s.xc, s.xc.shape, ddbc.shape[0]
+    if _OWN_DWX and ops.proj_wgrad_only_supported(xc, M, E, T):
+        if "x" not in slots:
+            slots["x"] = ops.wgrad_partials(T, E, M, xc.device, nsets=2)
+        ops.proj_wgrad_only(xc, ddbc, part=slots["x"][i])
+        return None
+    if _OWN_DWX and _own_wgrad_chunked_ok(xc, M):
+        return _own_wgrad_chunked(xc, ddbc)
+    return _wgrad_cm_cm(ddbc, xc)
+
+
+def _d_xc(s, du, ddbc, i, cache):
+    """d(xc) = du + W_x^T . d(dbc), in place in du (no copy of the 268 MB addend)."""
+    M, T = ddbc.shape
+    if ops.proj_wx_supported(du, M, T):
+        ops.proj_wx(_transposed(cache, "w_xT", s.w_x, i), ddbc, out=du, acc=du)
+    elif du.dtype == torch.float32:
+        ops.mm_f32(s.w_x.t(), ddbc, out=du, addend=du)
+    elif du.dtype == torch.float16:  # (shapes the fp16 MFMA kernel does not serve: the fp32 kernel on the exact widening)
+        du.copy_(ops.mm_f32(s.w_x.t().float(), ddbc.float(), addend=du.float()))
+    else:
+        du.addmm_(s.w_x.t(), ddbc)
+
+
+def _dx2d_is_streamed() -> bool:
+    return _OWN_GEMM
+
+
+def _d_x2d(dxz, w_in, cache):
+    """d(x2d) (T, D) token-major = dxz^T W_in (d_model 256: one 256-row tile, dxz read once; d_model 512: profiles/r05_gemm_stream_d512.txt)."""
+    dx2d = ops.proj_xTw_stream(_transposed(cache, "w_inT", w_in), dxz) if _dx2d_is_streamed() else None
+    return ops.mm(dxz.t(), w_in) if dx2d is None else dx2d
+
+
+def _dW_in_partials(dxz, x2d, glue):
+    """dW_in (2E, D) fp32 as a job of the fold of the weight-gradient partials, or None where its partial tiles are not served."""
+    part = ops.wgrad_cm_tm(dxz, x2d, return_partials=True) if (_GLUE_FOLD and _OWN_GEMM) else None
+    if part is None:
+        return None
+    dW_in = torch.empty((dxz.shape[0], x2d.shape[1]), dtype=torch.float32, device=x2d.device)
+    glue.append((part, dW_in, dW_in.numel(), part.shape[0], dW_in.numel(), 1, 0))
+    return dW_in
+
+
+def _wgrad_slot_sums(slots, glue):
+    """{"dt" / "x": (2, K, M) fp32 sums over the partial slots (2, P, K, M) of both sets} (fixed order) -- with _GLUE_FOLD as jobs of the
+    fold launch.  The slots hold (K, M); they are summed as they lie (a reduction over a permuted view runs at a quarter of the rate)."""
+    if not _GLUE_FOLD:
+        return {name: wg.sum(dim=1) for name, wg in slots.items()}
+    sums = {}
+    for name in ("dt", "x"):
+        if name in slots:
+            _, P, K, M = slots[name].shape
+            sums[name] = torch.empty((2, K, M), dtype=torch.float32, device=slots[name].device)
+            glue += [(src, dst, K * M, P, K * M, 1, 0) for src, dst in zip(slots[name], sums[name])]
+    return sums
 
 
 class BiMambaMixerFn(torch.autograd.Function):
@@ -276,327 +578,79 @@ class BiMambaMixerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2d, SB, Lq, split, cache, fp8_act, W_in, W_out, *ps):
-        lib = L.get_lib()
         act = x2d.dtype
-        T, Dm = x2d.shape
+        T = x2d.shape[0]
         E = W_in.shape[0] // 2
-        if cache is not None and cache["w"][0].dtype != act:
+        params, _ = _unflatten(SetParams, ps, 2)
+        if cache is not None and cache.w_in.dtype != act:
             cache = None
-        w_in = cache["w"][0] if cache else W_in.to(act)
-        w_out = cache["w"][1] if cache else W_out.to(act)
-        if _FP8_IN_PROJ and act == torch.bfloat16 and ops.fp8_proj_supported(x2d, Dm):
-            # fp8 matrix cores: per-token e4m3 activations x per-row e4m3 weights, fp32 accumulation, bf16 channel-major output
-            wq, sw = cache["w_in_fp8"] if (cache and "w_in_fp8" in cache) else ops.quant_weight_fp8(W_in)
-            # e4m3 activations + per-token scales: written by the add + norm kernel that produced x2d (fp8_act), else quantised here
-            xq, sx = (fp8_act[0].view(T, Dm), fp8_act[1]) if fp8_act is not None else ops.quant_rows_fp8(x2d)
-            xz = ops.proj_wxT_fp8(wq, sw, xq, sx).view(2 * E, SB, Lq)
-        else:
-            xz = None
-            if _STREAM_PROJ_D512 and Dm > 256 and act == torch.bfloat16:
-                w_inT = ((cache or {}).get("wT") or {}).get("in")
-                if w_inT is None:  # no step cache (eval, or parameters changed since prepare_step_cache): transpose here
-                    w_inT = w_in.t().contiguous()
-                # d_model 512: both operands streamed through the tiled kernel (A = tokens, B = W_in^T from the step cache), channel-major
-                # result (None if the shape is not served)
-                xz = ops.gemm_out_t(x2d, w_inT)
-            if xz is None and ops.proj_supported(x2d, Dm):  # bf16: the W-stationary MFMA kernel (csrc/gemm.hip) writes channel-major directly
-                xz = ops.proj_wxT(w_in, x2d)
-            if xz is None:
-                xz = ops.mm(w_in, x2d.t())  # fp32: cad_gemm_f32; a bf16 shape no own kernel serves: the library
-            xz = xz.view(2 * E, SB, Lq)
+        w_in = cache.w_in if cache else W_in.to(act)
+        w_out = cache.w_out if cache else W_out.to(act)
+        xz = _in_proj(x2d, W_in, w_in, cache, fp8_act).view(2 * E, SB, Lq)
         x, z = xz[:E], xz[E:]
-        sets, saved = [], []
-        dirs = ((0, 1), (1, 0))
-        cparams = []
-        for i in range(2):
-            conv_w, conv_b = ps[7 * i], ps[7 * i + 1]
-            cparams.append((conv_w.float().reshape(E, -1).contiguous(),
-                            None if conv_b is None else conv_b.float().contiguous()))
-        xcs = _conv_fwd2(x, cparams, split, dirs)
-        fused_sp = []
-        for i in range(2):
-            conv_w, conv_b, W_x, W_dt, dt_bias, A_log, Dp = ps[7 * i:7 * i + 7]
-            N, R = A_log.shape[1], W_dt.shape[1]
-            wf, bf = cparams[i]
-            xc = xcs[i]
-            w_x, w_dt = (cache["w"][2 + 2 * i], cache["w"][3 + 2 * i]) if cache else (W_x.to(act), W_dt.to(act))
-            if ops.proj_wx_supported(xc, E, T, M=R + 2 * N):  # thin-M / deep-K MFMA kernel: xc read once, W_x in LDS
-                dbc = ops.proj_wx(w_x, xc.view(E, T)).view(R + 2 * N, SB, Lq)
-            elif not _LIB_OUT_X_D512 and E % 128 == 0 and ops.proj_wx_supported(xc, E // 2, T, M=R + 2 * N):
-                # d_inner 1024 (configs[4]): 64 rows x 1024 of W_x do not fit LDS next to the X ring -- two K halves.  The first half is
-                # STORED in bf16 and widened again as the addend of the second, so dt_lr / B / C see two roundings (first half, then the
-                # sum), not one fp32 accumulation over K; xc is still read once
-                dbc = ops.proj_wx(w_x[:, :E // 2], xc.view(E, T)[:E // 2])
-                ops.proj_wx(w_x[:, E // 2:], xc.view(E, T)[E // 2:], out=dbc, acc=dbc)
-                dbc = dbc.view(R + 2 * N, SB, Lq)
-            else:
-                dbc = ops.mm(w_x, xc.view(E, T)).view(R + 2 * N, SB, Lq)
-            if ops.proj_wx_supported(xc, R, T):  # thin-K MFMA kernel (transposing LDS reads), csrc/gemm.hip
-                # ... with delta_bias + softplus in its epilogue (fp32): the scans take dt as it is (delta_is_dt)
-                delta = ops.proj_wx(w_dt, dbc[:R].view(R, T),
-                                    softplus_bias=dt_bias.float().contiguous() if _FUSED_SOFTPLUS else None).view(E, SB, Lq)
-                fused_sp.append(_FUSED_SOFTPLUS)
-            else:
-                delta = ops.mm(w_dt, dbc[:R].view(R, T)).view(E, SB, Lq)
-                fused_sp.append(False)
-            A = cache["A"][i] if cache else -torch.exp(A_log.float())
-            sets.append((xc, delta, A, dbc, Dp.float().contiguous(), dt_bias.float().contiguous(), wf, bf, w_x, w_dt))
-        # both parameter sets in one scan launch; k > 1: every row cut into k segments along L (ops.lsplit_factor) when the
-        # launch would otherwise leave CUs idle (Caduceus-Ph at batch 1)
+        cparams = [(p.conv_w.float().reshape(E, -1).contiguous(), None if p.conv_b is None else p.conv_b.float().contiguous())
+                   for p in params]
+        xcs = [xc.view(E, T) for xc in _conv_fwd2(x, cparams, split, _DIRS)]  # (from here on activations are (channels, T) views)
+        sets, delta_is_dt = [], []
+        for i, (p, xc, (conv_w, conv_b)) in enumerate(zip(params, xcs, cparams)):
+            w_x, w_dt = (cache.w_x[i], cache.w_dt[i]) if cache else (p.W_x.to(act), p.W_dt.to(act))
+            dbc = _x_proj(w_x, xc)
+            dt_bias = p.dt_bias.float().contiguous()
+            delta, fused = _dt_proj(w_dt, dbc[:w_dt.shape[1]], dt_bias)
+            A = cache.A[i] if cache else -torch.exp(p.A_log.float())
+            sets.append(SetSaved(xc, delta, A, dbc, p.D.float().contiguous(), dt_bias, conv_w, conv_b, w_x, w_dt, None, p.A_log))
+            delta_is_dt.append(fused)
         k = ops.lsplit_factor(E, SB, Lq, 2)
-        args = (L.ScanArgs * 2)()
-        outs, states = [], []
         ycat = torch.empty((2 * E, SB, Lq), dtype=act, device=x2d.device)  # [y_f ; y_r]: one out_proj GEMM with K = 2E
-        for i, (xc, delta, A, dbc, Df, bfz, *_rest) in enumerate(sets):
-            N, R = A.shape[1], dbc.shape[0] - 2 * A.shape[1]
-            out = ycat[i * E:(i + 1) * E]
-            state = torch.empty((lib.cad_scan_state_floats(E, SB * k, Lq // k, N),), dtype=torch.float32, device=xc.device)
-            Bm, Cm = dbc[R:R + N], dbc[R + N:]
-            stream = L.stream_and_check(xc, delta, A, Bm, Cm, Df, z, bfz, out, state)
-            args[i] = L.ScanArgs(L.ptr(xc), L.ptr(delta), L.ptr(A), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z), L.ptr(bfz),
-                                 L.ptr(out), L.ptr(state), SB * k, Lq // k, split * k, E, N, dirs[i][0], dirs[i][1],
-                                 L.dtype_code(act))
-            args[i].delta_is_dt = int(fused_sp[i])
-            outs.append(out)
-            states.append(state)
-        _keep, seg_P = ops.scan_fwd_launch(lib, args, 2, stream, k, [st[2] for st in sets], dirs, split)
-        y_f, y_r = outs
-        if _OWN_OUT_PROJ and ops.proj_xTw_supported(ycat, Dm, E, T):
-            # W_out (y_f + y_r): both panels through one set of resident W_out fragments, token-major output (cad_proj_xTw)
-            out2d = ops.proj_xTw(w_out, y_f.view(E, T), y_r.view(E, T))
-        else:
-            # d_model 512 (configs[4]): W_out is too deep for resident fragments -- both operands streamed (cad_gemm_stream), [y_f ; y_r]
-            # against [W_out, W_out] with K = 2 E; plain products for anything the kernel does not serve
-            out2d = None
-            if _STREAM_PROJ_D512 and not _LIB_OUT_X_D512 and act == torch.bfloat16:
-                w_out2 = (cache or {}).get("w_out2")
-                out2d = ops.proj_xTw_stream(w_out2 if w_out2 is not None else torch.cat([w_out, w_out], 1), ycat.view(2 * E, T))
-            if out2d is None:
-                out2d = ops.mm(ycat.view(2 * E, T).t(), torch.cat([w_out, w_out], 1).t())  # W_out (y_f + y_r), tied out_proj
-        wT = cache.get("wT") if cache else None
-        keep = [x2d, xz, w_in, w_out, ycat]
-        for i in range(2):
-            xc, delta, A, dbc, Df, bfz, wf, bf, w_x, w_dt = sets[i]
-            keep += [xc, delta, A, dbc, Df, bfz, wf, bf, w_x, w_dt, states[i], ps[7 * i + 5]]
-        ctx.wT = wT  # (not saved tensors: plain per-step copies owned by the cache)
-        ctx.save_for_backward(*keep, *seg_P)
-        ctx.meta = (SB, Lq, split, [tuple(None if p is None else (p.dtype, p.shape) for p in ps[7 * i:7 * i + 7])
-                                    for i in range(2)], W_in.dtype, W_out.dtype, tuple(fused_sp), k)
+        sets, seg_P = _scan_fwd(sets, z, ycat, delta_is_dt, split, k)
+        out2d = _out_proj(w_out, ycat.view(2 * E, T), cache)
+        ctx.cache = cache  # (not saved tensors: plain per-step copies owned by the cache)
+        ctx.save_for_backward(x2d, xz, w_in, w_out, ycat, *_flatten(sets), *seg_P)
+        ctx.meta = Meta(SB, Lq, split, [SetParams(*(None if t is None else t.dtype for t in p)) for p in params],
+                        [p.conv_w.shape for p in params], W_in.dtype, W_out.dtype, tuple(delta_is_dt), k)
         return out2d
 
     @staticmethod
     def backward(ctx, dout2d):
-        lib = L.get_lib()
         x2d, xz, w_in, w_out, ycat, *rest = ctx.saved_tensors
-        SB, Lq, split, pmeta, win_dt, wout_dt, fused_sp, k = ctx.meta
-        seg_P, rest = (rest[24:], rest[:24]) if k > 1 else ([], rest)
-        act = x2d.dtype
-        T, Dm = x2d.shape
+        sets, seg_P = _unflatten(SetSaved, rest, 2)
+        meta, cache = ctx.meta, ctx.cache
+        T = x2d.shape[0]
         E = xz.shape[0] // 2
-        x, z = xz[:E], xz[E:]
-        dirs = ((0, 1), (1, 0))
         dout2d = dout2d.contiguous()
-        # tied out_proj: the gradient w.r.t. y_f and y_r is the same tensor, produced channel-major
-        wT = ctx.wT
-        dy = None
-        if _STREAM_PROJ_D512 and Dm > 256 and act == torch.bfloat16:
-            dy = ops.gemm_out_t(dout2d, w_out)  # (T, D) @ W_out (D, E) -> (E, T): the weight as it lies is the row-major B operand
-        if dy is None and ops.proj_supported(dout2d, Dm):
-            dy = ops.proj_wxT(wT["out"] if wT else w_out.t().contiguous(), dout2d)
-        if dy is None:
-            dy = ops.mm(w_out.t(), dout2d.t())
-        dy = dy.view(E, SB, Lq)
-        y_f, y_r = ycat[:E], ycat[E:]
         glue = []  # (src, dst, n, nparts, stride, nparts2, stride2) jobs of the one fp32 fold launch at the end (_GLUE_FOLD)
-        part_out = None
-        if _GLUE_FOLD and _OWN_GEMM and (Dm <= 256 or _OWN_GEMM_D512):
-            part_out = ops.wgrad_cm_tm(ycat.view(2 * E, T), dout2d, return_partials=True)  # (slices, 2E, D)
-        if part_out is not None:
-            # both halves multiply the same tied weight: the fold adds them (second level) as it sums the slices
-            dW_out_ED = torch.empty((E, Dm), dtype=torch.float32, device=x2d.device)
-            glue.append((part_out, dW_out_ED, E * Dm, part_out.shape[0], 2 * E * Dm, 2, E * Dm))
-            dW_out = dW_out_ED.t()
-        else:
-            dW_cat = _wgrad_cm_tm(ycat.view(2 * E, T), dout2d)  # (2E, D): both halves multiply the same tied weight
-            dW_out = (dW_cat[:E] + dW_cat[E:]).t()
-        dxz = torch.empty_like(xz)       # [dx ; dz]: the gate z is shared, set 0's kernel writes the gradient of both gates
-        sets = [rest[12 * i:12 * i + 12] for i in range(2)]
-        args = (L.ScanBwdArgs * 2)()
-        work = []
-        zshapes = []
-        for i in range(2):  # per set: dA, dD, ddelta_bias (scan), dw, db (conv): accumulated by the kernels -> zeroed
-            _, _, A_, _, Df_, bfz_, wf_, bf_ = sets[i][:8]
-            zshapes += [A_.shape, Df_.shape, bfz_.shape, wf_.shape, (bf_.shape if bf_ is not None else (0,))]
-        zshapes += [(1,), (1,)]  # worklist counters of the exact z == 0 gate gradient (int32 views of zero bits)
-        N0 = sets[0][2].shape[1]
-        npart0 = lib.cad_scan_bwd_partials(E)
-        nch = max(1, (Lq // k) // int(lib.cad_scan_bwd_chunk_len()))
-        # (the fold follows the scan chunk by chunk with one workgroup per CU: it pays for long rows -- many chunks per (row, slice) item,
-        # few items per workgroup; short rows in large batches (configs[1]: 2 chunks, 64 items per workgroup) keep the streaming fold
-        # kernel behind the scan: 4.18 vs 4.83 ms per layer, profiles/r06_ab_stream_fold.txt)
-        stream_fold = (_STREAM_FOLD and sets[1][2].shape[1] == N0 and ops.fold_stream_supported(N0, npart0, Lq // k, act)
-                       and nch >= _STREAM_FOLD_MIN_CHUNKS and npart0 * SB * k * 2 <= 4 * ops._cu_count()
-                       and ops.fold_side_available(x2d.device))
-        if stream_fold:  # arrival counters (set, row, chunk) and give-up records (set, row, slice) of the concurrent fold: zero bits
-            nci = (int(lib.cad_scan_bwd_fold_counter_ints(SB * k, Lq // k)) + 3) // 4 * 4  # chunk arrivals + started count + CU marks
-            zshapes += [(2, nci), (2, SB * k, npart0)]
-        zbuf = _zeros_f32(zshapes, x2d.device)
-        fix_cnt = [zbuf[10].view(torch.int32), zbuf[11].view(torch.int32)]
-        n_fix = lib.cad_scan_gate_fix_entries(E, SB, Lq)
-        fix_list = [torch.empty((n_fix,), dtype=torch.int64, device=x2d.device) for _ in range(2)]
-        wg_dt = wg_x = None  # fp32 partial slots of the own weight-gradient kernels, both sets
-        for i in range(2):
-            xc, delta, A, dbc, Df, bfz, wf, bf, w_x, w_dt, state, A_log = sets[i]
-            N = A.shape[1]
-            R = dbc.shape[0] - 2 * N
-            du, ddelta = torch.empty_like(xc), torch.empty_like(xc)
-            dz = dxz[E:] if i == 0 else (None if _SHARED_GATE else torch.empty_like(z))
-            dz_r = dz if i == 1 else None
-            dA, dD, dbias = zbuf[5 * i:5 * i + 3]
-            npart = lib.cad_scan_bwd_partials(E)
-            dBC = torch.empty((2, npart, N, SB, Lq), dtype=ops.scan_slot_dtype(act), device=xc.device)
-            Bm, Cm = dbc[R:R + N], dbc[R + N:]
-            stream = L.stream_and_check(xc, delta, A, Bm, Cm, Df, z, bfz, dy, state, du, ddelta, dz, dA, dBC, dD, dbias)
-            args[i] = L.ScanBwdArgs(L.ptr(xc), L.ptr(delta), L.ptr(A), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z),
-                                    L.ptr(bfz), L.ptr(dy), L.ptr(y_f if i == 0 else y_r), L.ptr(state), L.ptr(du),
-                                    L.ptr(ddelta), L.ptr(dz), L.ptr(dA),
-                                    L.ptr(dBC[0]), L.ptr(dBC[1]), L.ptr(dD), L.ptr(dbias), SB * k, Lq // k, split * k, E, N,
-                                    dirs[i][0], dirs[i][1], L.dtype_code(act), npart, None, None,
-                                    L.ptr(y_r) if (i == 0 and _SHARED_GATE) else None, L.ptr(fix_list[i]),
-                                    L.ptr(fix_cnt[i]), L.ptr(dxz[E:]) if (_SHARED_GATE or i == 0) else L.ptr(dz))
-            args[i].delta_is_dt = int(fused_sp[i])
-            if stream_fold:
-                args[i].fold_counters = L.ptr(zbuf[12][i])
-            work.append((du, ddelta, dA, dD, dbias, dBC, npart))
-        # the dB / dC partial slots of BOTH sets are folded straight into the rows of each set's x_proj gradient operand ...
-        ddbcs = [torch.empty_like(sets[i][3]) for i in range(2)]
-        launch_scan = lambda: ops.scan_bwd_launch(lib, args, 2, stream, k, seg_P, dirs, split)
-        if stream_fold:
-            # ... chunk by chunk on a second stream while the scan still runs (cad_fold_partials_stream)
-            fargs = (L.FoldArgs * 2)()
-            for i in range(2):
-                N_, R_ = sets[i][2].shape[1], sets[i][3].shape[0] - 2 * sets[i][2].shape[1]
-                dBC_ = work[i][5]
-                fargs[i] = L.FoldArgs(L.ptr(dBC_[0]), L.ptr(dBC_[1]), L.ptr(ddbcs[i][R_:R_ + N_]), L.ptr(ddbcs[i][R_ + N_:]),
-                                      L.ptr(zbuf[12][i]), L.ptr(zbuf[13][i]), SB * k, Lq // k, split * k, N_, work[i][6],
-                                      dirs[i][0], dirs[i][1], L.dtype_code(act))
-            _keep = ops.fold_behind_scan(lib, fargs, 2, x2d.device, launch_scan, give_ups=zbuf[13])
-        else:
-            _keep = launch_scan()
-        L.check(lib.cad_scan_bwd_gate_fix(args, 2, stream), "cad_scan_bwd_gate_fix")  # no-op unless some gate is lost (z == 0; fp16: |z| <= 2^-15)
-        grads, dxcs, part = [], [], []
-        if not stream_fold:
-            # ... by one launch behind the scan (four folds: cad_reduce_partials_multi)
-            jobs = (L.ReduceJob * 4)()
-            for i in range(2):
-                N_, R_ = sets[i][2].shape[1], sets[i][3].shape[0] - 2 * sets[i][2].shape[1]
-                dBC_ = work[i][5]
-                jobs[2 * i] = L.ReduceJob(L.ptr(dBC_[0]), L.ptr(ddbcs[i][R_:R_ + N_]))
-                jobs[2 * i + 1] = L.ReduceJob(L.ptr(dBC_[1]), L.ptr(ddbcs[i][R_ + N_:]))
-            assert work[0][6] == work[1][6] and sets[0][2].shape[1] == sets[1][2].shape[1], "one fold launch: both sets share depth and d_state"
-            L.check(lib.cad_reduce_partials_multi(jobs, 4, work[0][6], sets[0][2].shape[1] * SB * Lq, L.dtype_code(act), stream),
-                    "cad_reduce_partials_multi")
-        for i in range(2):
-            xc, delta, A, dbc, Df, bfz, wf, bf, w_x, w_dt, state, A_log = sets[i]
-            du, ddelta, dA, dD, dbias, dBC, npart = work[i]
-            N = A.shape[1]
-            R = dbc.shape[0] - 2 * N
-            # gradient of [dt_lr ; B ; C] assembled in place: rows [R:] by the partial-slot reduction, rows [:R] by a GEMM
-            ddbc = ddbcs[i]
-            if _FUSED_WGRAD and ops.proj_wx_wgrad_supported(ddelta, R, E, T):
-                # d(dt_lr) = W_dt^T d(delta) and dW_dt = d(delta) dt_lr^T from ONE pass over d(delta) (cad_proj_wx_wgrad); the
-                # partial slots of both parameter sets are folded by one sum after the loop
-                if wg_dt is None:
-                    wg_dt = ops.wgrad_partials(T, E, R, xc.device, nsets=2)
-                ops.proj_wx_wgrad(wT["dt"][i] if wT else w_dt.t().contiguous(), ddelta.view(E, T),
-                                  dbc[:R].view(R, T), out=ddbc[:R].view(R, T), part=wg_dt[i])
-                dW_dt = None
-            else:
-                if ops.proj_wx_supported(ddelta, E, T, M=R):
-                    ops.proj_wx(wT["dt"][i] if wT else w_dt.t().contiguous(), ddelta.view(E, T), out=ddbc[:R].view(R, T))
-                else:
-                    ops.mm(w_dt.t(), ddelta.view(E, T), out=ddbc[:R].view(R, T))
-                if _OWN_DWX and _own_wgrad_chunked_ok(ddelta.view(E, T), R):
-                    dW_dt = _own_wgrad_chunked(ddelta.view(E, T), dbc[:R].view(R, T)).t()
-                else:
-                    dW_dt = _wgrad_cm_cm(ddelta.view(E, T), dbc[:R].view(R, T))
-            if _OWN_DWX and ops.proj_wgrad_only_supported(xc, R + 2 * N, E, T):
-                if wg_x is None:
-                    wg_x = ops.wgrad_partials(T, E, R + 2 * N, xc.device, nsets=2)
-                ops.proj_wgrad_only(xc.view(E, T), ddbc.view(R + 2 * N, T), part=wg_x[i])
-                dW_x = None
-            elif _OWN_DWX and _own_wgrad_chunked_ok(xc.view(E, T), R + 2 * N):
-                dW_x = _own_wgrad_chunked(xc.view(E, T), ddbc.view(R + 2 * N, T))
-            else:
-                dW_x = _wgrad_cm_cm(ddbc.view(R + 2 * N, T), xc.view(E, T))
-            # d(xc) = du + W_x^T . d(dbc), in place (no copy of the 268 MB addend)
-            if ops.proj_wx_supported(du, R + 2 * N, T):
-                ops.proj_wx(wT["x"][i] if wT else w_x.t().contiguous(), ddbc.view(R + 2 * N, T), out=du.view(E, T),
-                            acc=du.view(E, T))
-            else:
-                if du.dtype == torch.float32:
-                    ops.mm_f32(w_x.t(), ddbc.view(R + 2 * N, T), out=du.view(E, T), addend=du.view(E, T))
-                elif du.dtype == torch.float16:  # (shapes the fp16 MFMA kernel does not serve: the fp32 kernel on the exact widening)
-                    du.view(E, T).copy_(ops.mm_f32(w_x.t().float(), ddbc.view(R + 2 * N, T).float(), addend=du.view(E, T).float()))
-                else:
-                    du.view(E, T).addmm_(w_x.t(), ddbc.view(R + 2 * N, T))
-            dxcs.append(du)
-            part.append((dW_x, dW_dt, dbias, dA * A, dD))  # A = -exp(A_log)  =>  dA/dA_log = A
+        slots = {}  # "dt" / "x": fp32 partial slots of the own weight-gradient kernels, both sets (allocated by the first set that uses them)
+        dy = _d_y(dout2d, w_out, cache)
+        dW_out = _dW_out(ycat.view(2 * E, T), dout2d, glue)
+        dxz, work, ddbcs, conv_bufs = _scan_bwd(sets, xz, ycat, dy, seg_P, meta)
+        part = []
+        for i, (s, w, ddbc) in enumerate(zip(sets, work, ddbcs)):
+            dW_dt = _d_dt_lr(s, w, ddbc, i, cache, slots)
+            dW_x = _dW_x(s, ddbc, i, slots)
+            _d_xc(s, w.du, ddbc, i, cache)
+            part.append((dW_x, dW_dt, w.dA * s.A))  # A = -exp(A_log)  =>  dA/dA_log = A
         if CAPTURE_XPROJ_OPERANDS is not None:
-            CAPTURE_XPROJ_OPERANDS.append({"ddbc": [d.reshape(d.shape[0], T).clone() for d in ddbcs],
-                                           "xc": [sets[i][0].reshape(E, T).clone() for i in range(2)]})
-        conv_g = _conv_bwd2(x, [(sets[i][6], sets[i][7]) for i in range(2)], dxcs, dxz[:E], split, dirs,
-                            bufs=[(zbuf[5 * i + 3], zbuf[5 * i + 4] if sets[i][7] is not None else None) for i in range(2)])
-        # one fold per weight for BOTH sets' partial slots (fixed order): (2, P, K, M) -> (2, K, M) / (2, M, K)
-        # (the slots hold (K, M); summed as they lie -- a reduction over a permuted view runs at a quarter of the rate -- and the
-        # small (2, K, M) result is transposed)
-        sum_dt = sum_x_km = None
-        if _GLUE_FOLD:
-            for wg, name in ((wg_dt, "dt"), (wg_x, "x")):
-                if wg is not None:
-                    _, P_, K_, M_ = wg.shape
-                    res = torch.empty((2, K_, M_), dtype=torch.float32, device=x2d.device)
-                    for i in range(2):
-                        glue.append((wg[i], res[i], K_ * M_, P_, K_ * M_, 1, 0))
-                    if name == "dt":
-                        sum_dt = res
-                    else:
-                        sum_x_km = res
-        else:
-            sum_dt = None if wg_dt is None else wg_dt.sum(dim=1)
-            sum_x_km = None if wg_x is None else wg_x.sum(dim=1)
-        if dz_r is not None:
-            dxz[E:].add_(dz_r)
-        # d(x2d) and dW_in first (the fold launch below reads dW_in's partial tiles)
-        # (d_model 256: one 256-row tile, dxz read once; d_model 512: profiles/r05_gemm_stream_d512.txt)
-        dx2d = None
-        if _OWN_GEMM and (Dm <= 256 or _OWN_GEMM_D512):
-            w_inT = wT["in"] if (wT and wT.get("in") is not None) else w_in.t().contiguous()
-            dx2d = ops.proj_xTw_stream(w_inT, dxz.view(2 * E, T))
-        if dx2d is None:
-            dx2d = ops.mm(dxz.view(2 * E, T).t(), w_in)
-        part_in = None
-        if _GLUE_FOLD and _OWN_GEMM and (Dm <= 256 or _OWN_GEMM_D512):
-            part_in = ops.wgrad_cm_tm(dxz.view(2 * E, T), x2d, return_partials=True)
-        if part_in is not None:
-            dW_in = torch.empty((2 * E, Dm), dtype=torch.float32, device=x2d.device)
-            glue.append((part_in, dW_in, 2 * E * Dm, part_in.shape[0], 2 * E * Dm, 1, 0))
-        else:
-            dW_in = None
+            CAPTURE_XPROJ_OPERANDS.append({"ddbc": [d.clone() for d in ddbcs], "xc": [s.xc.clone() for s in sets]})
+        conv_g = _conv_bwd2(xz[:E], [(s.conv_w, s.conv_b) for s in sets], [w.du for w in work], dxz[:E], meta.split, _DIRS,
+                            bufs=conv_bufs)
+        sums = _wgrad_slot_sums(slots, glue)
+        # d(x2d) and dW_in first: the fold launch below reads dW_in's partial tiles
+        dx2d = _d_x2d(dxz.view(2 * E, T), w_in, cache)
+        dW_in = _dW_in_partials(dxz.view(2 * E, T), x2d, glue)
         if glue:
             ops.fold_f32(glue)
-        sum_x = None if sum_x_km is None else sum_x_km.transpose(1, 2).contiguous()
-        for i in range(2):
-            meta = pmeta[i]
-            (dwc, dbc_conv), (dW_x, dW_dt, dbias, dA_log, dD) = conv_g[i], part[i]
-            dW_x = sum_x[i] if dW_x is None else dW_x
-            dW_dt = sum_dt[i] if dW_dt is None else dW_dt
-            grads += [dwc.reshape(meta[0][1]).to(meta[0][0]), None if dbc_conv is None else dbc_conv.to(meta[1][0]),
-                      dW_x.to(meta[2][0]), dW_dt.to(meta[3][0]), dbias.to(meta[4][0]), dA_log.to(meta[5][0]),
-                      dD.to(meta[6][0])]
+        if "x" in sums:
+            sums["x"] = sums["x"].transpose(1, 2).contiguous()  # (the small (2, K, M) result is transposed, not the slots)
+        grads = []
+        for i, (dt, (dwc, dbc_conv), (dW_x, dW_dt, dA_log), w) in enumerate(zip(meta.pdtypes, conv_g, part, work)):
+            dW_x = sums["x"][i] if dW_x is None else dW_x
+            dW_dt = sums["dt"][i] if dW_dt is None else dW_dt
+            grads += SetParams(conv_w=dwc.reshape(meta.conv_w_shapes[i]).to(dt.conv_w),
+                               conv_b=None if dbc_conv is None else dbc_conv.to(dt.conv_b), W_x=dW_x.to(dt.W_x), W_dt=dW_dt.to(dt.W_dt),
+                               dt_bias=w.dbias.to(dt.dt_bias), A_log=dA_log.to(dt.A_log), D=w.dD.to(dt.D))
         if dW_in is None:
             dW_in = _wgrad_cm_tm(dxz.view(2 * E, T), x2d)
-        return (dx2d, None, None, None, None, None, dW_in.to(win_dt), dW_out.to(wout_dt), *grads)
+        return (dx2d, None, None, None, None, None, dW_in.to(meta.win_dt), dW_out.to(meta.wout_dt), *grads)
 
 
 def can_use(mamba_fwd, mamba_rev, strategy) -> bool:
@@ -611,9 +665,8 @@ def can_use(mamba_fwd, mamba_rev, strategy) -> bool:
 
 def bimamba_mixer(hn: torch.Tensor, mamba_fwd, mamba_rev, split: int) -> torch.Tensor:
     S, B, Lq, Dm = hn.shape
-    ps = []
-    for m in (mamba_fwd, mamba_rev):
-        ps += [m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, m.A_log, m.D]
+    ps = _flatten(SetParams(m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, m.A_log, m.D)
+                  for m in (mamba_fwd, mamba_rev))
     cache = _cached(mamba_fwd, [mamba_fwd.in_proj.weight, mamba_fwd.out_proj.weight, mamba_fwd.x_proj.weight,
                                 mamba_fwd.dt_proj.weight, mamba_rev.x_proj.weight, mamba_rev.dt_proj.weight,
                                 mamba_fwd.A_log, mamba_rev.A_log])

@@ -380,10 +380,11 @@ FOLD_GIVE_UPS = None  # a list: every device launch appends the number of give-u
 
 
 def _count_give_ups(give_ups):
-    """Diagnostics (tests, tools): the slices the concurrent pass left to the cleanup.  The records are int32 (chunk + 1) -- counted on
-    the integer view: read as fp32 they are denormals, which a flush-to-zero count would miss."""
+    """Diagnostics (tests, tools): the slices the concurrent pass left to the cleanup.  The records are int32 (chunk + 1) and are
+    counted as such: read as fp32 they are denormals, which a flush-to-zero count would miss."""
     if FOLD_GIVE_UPS is not None and give_ups is not None:
-        FOLD_GIVE_UPS.append(torch.count_nonzero(give_ups.view(torch.int32)))
+        assert give_ups.dtype == torch.int32
+        FOLD_GIVE_UPS.append(torch.count_nonzero(give_ups))
 
 
 def fold_behind_scan(lib, fold_args, nsets: int, device, launch_scan, give_ups=None):
