@@ -657,7 +657,9 @@ class _LmHead(torch.autograd.Function):
             valid = ((lab != ignore_index) & (lab >= 0) & (lab < V)).to(torch.float32).unsqueeze(1)  # as the forward counts
             sm = torch.softmax(logits.reshape(-1, V), dim=-1)
             sm.scatter_add_(1, lab.clamp(0, V - 1).unsqueeze(1), -valid)  # rows that do not count add -0 somewhere
-            sm.mul_(valid * (dloss / acc[1]))
+            # rows that do not count get an exact 0, not 0 * coefficient: with every label ignored the coefficient is 1 / 0, and
+            # F.cross_entropy (like cad_lm_head_bwd) then returns zero gradients beside its NaN loss
+            sm.mul_(dloss / acc[1]).masked_fill_(valid == 0, 0.0)
             g = sm if g is None else g + sm
         if g is None:
             g = torch.zeros((logits.numel() // V, V), dtype=torch.float32, device=hidden.device)

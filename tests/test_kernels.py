@@ -242,7 +242,8 @@ def test_embed(backend, n_strands, D):
 @pytest.mark.parametrize("V,D,B,L", [(16, 40, 2, 300), (16, 256, 2, 301), (12, 128, 1, 75), (16, 256, 1, 9000), (16, 512, 1, 200)])
 def test_lm_head_and_loss(backend, n_strands, dtype, V, D, B, L):
     """D = 40: the general kernel; D = 128 / 256: the matrix-core kernel (fp32 MFMA, 16-token tiles -- ragged last tile, a vocabulary
-    smaller than the tile, enough tiles for several per wave); D = 512: the backward as two launches over blocks of 256 channels."""
+    smaller than the tile; L = 9000 is 563 tiles on 141 workgroups of 4 waves, still ONE tile per wave -- a wave takes a second tile only
+    above 32768 tokens, tests/test_norm_head_fp64.py); D = 512: the backward as two launches over blocks of 256 channels."""
     name, dev = backend
     g = torch.Generator().manual_seed(2)
     comp = torch.tensor([0, 1, 2, 3, 4, 5, 6, 10, 9, 8, 7, 11, 12, 13, 14, 15])[:V]
