@@ -354,10 +354,8 @@ def _scan_fwd(sets, z, ycat, delta_is_dt, split, k):
         R = s.dbc.shape[0] - 2 * N
         state = torch.empty((lib.cad_scan_state_floats(E, SB * k, Lq // k, N),), dtype=torch.float32, device=z.device)
         Bm, Cm = s.dbc[R:R + N], s.dbc[R + N:]
-        stream = L.stream_and_check(s.xc, s.delta, s.A, Bm, Cm, s.D, z, s.dt_bias, out, state)
-        args[i] = L.ScanArgs(L.ptr(s.xc), L.ptr(s.delta), L.ptr(s.A), L.ptr(Bm), L.ptr(Cm), L.ptr(s.D), L.ptr(z), L.ptr(s.dt_bias),
-                             L.ptr(out), L.ptr(state), SB * k, Lq // k, split * k, E, N, *_DIRS[i], L.dtype_code(z.dtype))
-        args[i].delta_is_dt = int(delta_is_dt[i])
+        args[i], stream = ops.scan_fwd_args(E, SB, Lq, N, split, _DIRS[i], z.dtype, k=k, delta_is_dt=delta_is_dt[i], u=s.xc, delta=s.delta,
+                                            A=s.A, Bm=Bm, Cm=Cm, D=s.D, z=z, delta_bias=s.dt_bias, out=out, chunk_state=state)
         with_state.append(s._replace(state=state))
     _keep, seg_P = ops.scan_fwd_launch(lib, args, 2, stream, k, [s.A for s in sets], _DIRS, split)
     return with_state, seg_P
@@ -447,21 +445,17 @@ def _scan_bwd(sets, xz, ycat, dy, seg_P, meta):
     for i, (s, y) in enumerate(zip(sets, ycat.view(2, E, SB, Lq))):
         N = s.A.shape[1]
         R = s.dbc.shape[0] - 2 * N
-        np_i = lib.cad_scan_bwd_partials(E)
+        np_i = lib.cad_scan_bwd_partials(E)  # (asked once per set on top of `npart`: the pinned schedule keeps the three queries)
         w = SetWork(torch.empty_like(s.xc), torch.empty_like(s.xc), zero["dA", i], zero["dD", i], zero["dbias", i],
                     torch.empty((2, np_i, N, SB, Lq), dtype=ops.scan_slot_dtype(act), device=dev), np_i)
         dz = dxz[E:] if i == 0 else None
         Bm, Cm = s.dbc[R:R + N], s.dbc[R + N:]
-        stream = L.stream_and_check(s.xc, s.delta, s.A, Bm, Cm, s.D, z, s.dt_bias, dy, s.state, w.du, w.ddelta, dz, w.dA, w.dBC, w.dD,
-                                    w.dbias)
-        args[i] = L.ScanBwdArgs(L.ptr(s.xc), L.ptr(s.delta), L.ptr(s.A), L.ptr(Bm), L.ptr(Cm), L.ptr(s.D), L.ptr(z), L.ptr(s.dt_bias),
-                                L.ptr(dy), L.ptr(y), L.ptr(s.state), L.ptr(w.du), L.ptr(w.ddelta), L.ptr(dz), L.ptr(w.dA),
-                                *map(L.ptr, w.dBC), L.ptr(w.dD), L.ptr(w.dbias), SB * k, Lq // k, split * k, E, N, *_DIRS[i],
-                                L.dtype_code(act), w.npart, None, None, L.ptr(ycat[E:]) if i == 0 else None, L.ptr(fix_list[i]),
-                                L.ptr(zero["fix_cnt", i]), L.ptr(dxz[E:]))
-        args[i].delta_is_dt = int(meta.delta_is_dt[i])
-        if stream_fold:
-            args[i].fold_counters = L.ptr(zero["fold_counters"][i])
+        args[i], stream = ops.scan_bwd_args(E, SB, Lq, N, split, _DIRS[i], act, w.npart, k=k, delta_is_dt=meta.delta_is_dt[i], u=s.xc,
+                                            delta=s.delta, A=s.A, Bm=Bm, Cm=Cm, D=s.D, z=z, delta_bias=s.dt_bias, dout=dy, out=y,
+                                            chunk_state=s.state, du=w.du, ddelta=w.ddelta, dz=dz, dA=w.dA, dB=w.dBC[0], dC=w.dBC[1],
+                                            dD=w.dD, ddelta_bias=w.dbias, out2=ycat[E:] if i == 0 else None, gate_fix_list=fix_list[i],
+                                            gate_fix_count=zero["fix_cnt", i], gate_fix_dz=dxz[E:],
+                                            fold_counters=zero["fold_counters"][i] if stream_fold else None)
         work.append(w)
     ddbcs = [torch.empty_like(s.dbc) for s in sets]
     rows = []  # per set: (dB slots, dC slots, dB rows of d(dbc), dC rows of d(dbc))

@@ -226,6 +226,10 @@ def causal_conv1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
 # ------------------------------------------------------------------------------------------------------------------
 # selective scan
 # ------------------------------------------------------------------------------------------------------------------
+# Every caller of the scan kernels (the autograd functions below, seqpar._ScanSeqPar, the mixer's _scan_fwd / _scan_bwd) fills
+# cad_scan_args / cad_scan_bwd_args through scan_fwd_args / scan_bwd_args: tensors by field name, absent fields NULL, the L-split
+# reshaping applied in that one place.  The autograd functions also share their backward: scan_bwd_sets (outputs + structs),
+# fold_dBC and scan_bwd_grads (parameter-dtype casts, dz over the sets); each keeps its own launches.
 # ---- L-split (two-pass) scans on one GPU --------------------------------------------------------------------------------
 # A scan launch has ceil(E / 8) * rows * sets workgroups -- 256 for Caduceus-PS at batch 1, i.e. one per CU, but only 128 for
 # Caduceus-Ph or a uni-directional model at batch 1.  When fewer than ~one workgroup per CU exist,
@@ -420,94 +424,127 @@ def gate_fix_buffers(lib, u, N):
     return lst, cnt
 
 
+_SCAN_PTRS = {cls: frozenset(f for f, t in cls._fields_ if t is C.c_void_p) for cls in (L.ScanArgs, L.ScanBwdArgs)}
+
+
+def _scan_struct(cls, E, SB, Lq, N, split, dirs, act, k, ints, tensors):
+    if not tensors.keys() <= _SCAN_PTRS[cls]:  # (ctypes would take a misspelt field as a plain attribute)
+        raise TypeError(f"{cls.__name__} has no pointer field {sorted(tensors.keys() - _SCAN_PTRS[cls])}")
+    stream = L.stream_and_check(*tensors.values())
+    return cls(SB=SB * k, L=Lq // k, split=split * k, E=E, N=N, rev_lo=dirs[0], rev_hi=dirs[1], dtype=L.dtype_code(act), **ints,
+               **{f: L.ptr(t) for f, t in tensors.items()}), stream
+
+
+def scan_fwd_args(E, SB, Lq, N, split, dirs, act, *, k=1, delta_is_dt=False, **tensors):
+    """(cad_scan_args, launch stream) of one parameter set: rows (E, SB, Lq) of dtype `act`, dirs = (rev_lo, rev_hi), every row cut into
+    k segments along L.  tensors: the struct's pointer fields by name (u=, delta=, ..., h0=, hT=, sum_dt=); None or absent stays NULL."""
+    return _scan_struct(L.ScanArgs, E, SB, Lq, N, split, dirs, act, k, dict(delta_is_dt=int(bool(delta_is_dt))), tensors)
+
+
+def scan_bwd_args(E, SB, Lq, N, split, dirs, act, n_partials, *, k=1, delta_is_dt=False, **tensors):
+    """(cad_scan_bwd_args, launch stream), as scan_fwd_args; n_partials: the depth of the dB / dC slots (cad_scan_bwd_partials)."""
+    return _scan_struct(L.ScanBwdArgs, E, SB, Lq, N, split, dirs, act, k,
+                        dict(n_partials=n_partials, delta_is_dt=int(bool(delta_is_dt))), tensors)
+
+
+def scan_inputs(z, tensors):
+    """(contiguous z, [(u, delta, A, Bm, Cm, D, delta_bias)] as the kernels take them: contiguous, parameters in fp32)."""
+    z = None if z is None else z.contiguous()
+    sets = []
+    for i in range(0, len(tensors), 7):
+        u, delta, A, Bm, Cm, D, bias = tensors[i:i + 7]
+        if delta.dtype != u.dtype or Bm.dtype != u.dtype or Cm.dtype != u.dtype or (z is not None and z.dtype != u.dtype):
+            raise TypeError("selective_scan: u, delta, B, C, z must share one dtype")
+        sets.append((u.contiguous(), delta.contiguous(), A.float().contiguous(), Bm.contiguous(), Cm.contiguous(),
+                     D.float().contiguous(), bias.float().contiguous()))
+    return z, sets
+
+
+def scan_param_dtypes(tensors):
+    return [(tensors[i + 2].dtype, tensors[i + 5].dtype, tensors[i + 6].dtype) for i in range(0, len(tensors), 7)]
+
+
+def scan_bwd_sets(lib, sets, z, douts, split, dirs, *, k=1, delta_is_dt=False, npart=None, dhTs=None, dh0=False, gate_fix):
+    """Argument structs of the scan backward with freshly allocated outputs.  sets[i]: (u, delta, A, Bm, Cm, D, delta_bias, chunk_state,
+    out) as the forward saved them.  npart: the slot depth where the caller has asked for it already; gate_fix: the exact-gate worklist
+    (used with a gate only), or None.  Returns (struct array, per set ({field: output}, dB / dC slots), stream)."""
+    args, res = (L.ScanBwdArgs * len(sets))(), []
+    for i, (u, delta, A, Bm, Cm, D, bias, state, fout) in enumerate(sets):
+        (E, SB, Lq), N = u.shape, A.shape[1]
+        np_i = lib.cad_scan_bwd_partials(E) if npart is None else npart  # one partial-sum slot per workgroup (written, not accumulated)
+        dBC = torch.empty((2, np_i, N, SB, Lq), dtype=scan_slot_dtype(u.dtype), device=u.device)
+        o = dict(du=torch.empty_like(u), ddelta=torch.empty_like(u), dz=None if z is None else torch.empty_like(u),
+                 dA=torch.zeros_like(A), dB=dBC[0], dC=dBC[1], dD=torch.zeros_like(D), ddelta_bias=torch.zeros_like(bias))
+        if dh0:
+            o["dh0"] = torch.empty((E, SB, N), dtype=torch.float32, device=u.device)
+        if gate_fix is not None and z is not None:
+            o["gate_fix_list"], o["gate_fix_count"] = gate_fix(lib, u, N)
+            o["gate_fix_dz"] = o["dz"]
+        args[i], stream = scan_bwd_args(E, SB, Lq, N, split, dirs[i], u.dtype, np_i, k=k, delta_is_dt=delta_is_dt, u=u, delta=delta,
+                                        A=A, Bm=Bm, Cm=Cm, D=D, z=z, delta_bias=bias, dout=douts[i], out=fout, chunk_state=state,
+                                        dhT=dhTs[i] if dhTs else None, **o)
+        res.append((o, dBC))
+    return args, res, stream
+
+
+def fold_dBC(dBC, act, stream):
+    """(dB, dC) (N, SB, L) in `act` from the (2, npart, N, SB, L) partial slots of one set: one fold launch each."""
+    npart, n = dBC.shape[1], dBC[0, 0].numel()
+    dB, dC = (torch.empty(dBC.shape[2:], dtype=act, device=dBC.device) for _ in range(2))
+    for src, dst in ((dBC[0], dB), (dBC[1], dC)):
+        L.check(L.get_lib().cad_reduce_partials(L.ptr(src), npart, n, L.ptr(dst), L.dtype_code(act), stream), "cad_reduce_partials")
+    return dB, dC
+
+
+def scan_bwd_grads(res, pdt, stream, dz_in_place=True):
+    """([du, ddelta, dA, dB, dC, dD, ddelta_bias] per set, parameter gradients in the parameters' dtypes pdt[i]; dz summed over the sets
+    that share the gate, or None)."""
+    grads, dz_tot = [], None
+    for (o, dBC), (Adt, Ddt, bdt) in zip(res, pdt):
+        dB, dC = fold_dBC(dBC, o["du"].dtype, stream)
+        grads.append([o["du"], o["ddelta"], o["dA"].to(Adt), dB, dC, o["dD"].to(Ddt), o["ddelta_bias"].to(bdt)])
+        if o["dz"] is not None:
+            dz_tot = o["dz"] if dz_tot is None else (dz_tot.add_(o["dz"]) if dz_in_place else dz_tot + o["dz"])
+    return grads, dz_tot
+
+
 class _ScanMulti(torch.autograd.Function):
     """1 or 2 parameter sets (same shapes, shared gate z) in one launch.  Tensor args per set:
     u, delta, A, Bm, Cm, D, delta_bias."""
 
     @staticmethod
     def forward(ctx, z, split, dirs, delta_is_dt, *tensors):
-        nsets = len(tensors) // 7
         lib = L.get_lib()
-        z = None if z is None else z.contiguous()
-        sets, args = [], (L.ScanArgs * nsets)()
-        need_grad = any(ctx.needs_input_grad)
-        outs = []
-        for i in range(nsets):
-            u, delta, A, Bm, Cm, D, bias = tensors[7 * i:7 * i + 7]
-            u, delta, Bm, Cm = u.contiguous(), delta.contiguous(), Bm.contiguous(), Cm.contiguous()
-            if delta.dtype != u.dtype or Bm.dtype != u.dtype or Cm.dtype != u.dtype or \
-                    (z is not None and z.dtype != u.dtype):
-                raise TypeError("selective_scan: u, delta, B, C, z must share one dtype")
-            E, SB, Lq = u.shape
-            N = A.shape[1]
+        z, sets = scan_inputs(z, tensors)
+        nsets = len(sets)
+        args, saved = (L.ScanArgs * nsets)(), []
+        for i, (u, delta, A, Bm, Cm, D, bias) in enumerate(sets):
+            (E, SB, Lq), N = u.shape, A.shape[1]
             k = lsplit_factor(E, SB, Lq, nsets)  # same shapes in every set -> same k
-            Af, Df, bf = A.float().contiguous(), D.float().contiguous(), bias.float().contiguous()
             out = torch.empty_like(u)
             state = (torch.empty((lib.cad_scan_state_floats(E, SB * k, Lq // k, N),), dtype=torch.float32, device=u.device)
-                     if need_grad else None)
-            stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, out, state)
-            rl, rh = dirs[i]
-            args[i] = L.ScanArgs(L.ptr(u), L.ptr(delta), L.ptr(Af), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z), L.ptr(bf),
-                                 L.ptr(out), L.ptr(state), SB * k, Lq // k, split * k, E, N, rl, rh, L.dtype_code(u.dtype))
-            args[i].delta_is_dt = int(bool(delta_is_dt))
-            sets.append((u, delta, Af, Bm, Cm, Df, bf, state, out))
-            outs.append(out)
-        _keep, Ps = scan_fwd_launch(lib, args, nsets, stream, k, [s_[2] for s_ in sets], dirs, split)
-        flat = [t for s_ in sets for t in s_]
-        ctx.save_for_backward(z, *flat, *Ps)
-        ctx.meta = (split, dirs, nsets, [(t[2].dtype, t[5].dtype, t[6].dtype) for t in
-                                         [tensors[7 * i:7 * i + 7] for i in range(nsets)]], bool(delta_is_dt), k)
-        return tuple(outs)
+                     if any(ctx.needs_input_grad) else None)
+            args[i], stream = scan_fwd_args(E, SB, Lq, N, split, dirs[i], u.dtype, k=k, delta_is_dt=delta_is_dt, u=u, delta=delta, A=A,
+                                            Bm=Bm, Cm=Cm, D=D, z=z, delta_bias=bias, out=out, chunk_state=state)
+            saved += [*sets[i], state, out]
+        _keep, Ps = scan_fwd_launch(lib, args, nsets, stream, k, [s[2] for s in sets], dirs, split)
+        ctx.save_for_backward(z, *saved, *Ps)
+        ctx.meta = (split, dirs, nsets, scan_param_dtypes(tensors), delta_is_dt, k)
+        return tuple(saved[8::9])
 
     @staticmethod
     def backward(ctx, *douts):
         z, *flat = ctx.saved_tensors
         split, dirs, nsets, pdt, delta_is_dt, k = ctx.meta
-        Ps, flat = (flat[9 * nsets:], flat[:9 * nsets]) if k > 1 else ([], flat)
         lib = L.get_lib()
-        args = (L.ScanBwdArgs * nsets)()
-        keep, res = [], []
-        for i in range(nsets):
-            u, delta, Af, Bm, Cm, Df, bf, state, fout = flat[9 * i:9 * i + 9]
-            E, SB, Lq = u.shape
-            N = Af.shape[1]
-            dout = douts[i].contiguous()
-            du, ddelta = torch.empty_like(u), torch.empty_like(u)
-            dz = None if z is None else torch.empty_like(u)
-            dA, dD, dbias = torch.zeros_like(Af), torch.zeros_like(Df), torch.zeros_like(bf)
-            npart = lib.cad_scan_bwd_partials(E)  # one partial-sum slot per workgroup (written, not accumulated)
-            dBC = torch.empty((2, npart, N, SB, Lq), dtype=scan_slot_dtype(u.dtype), device=u.device)
-            stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, dout, state, du, ddelta, dz, dA, dBC, dD, dbias)
-            rl, rh = dirs[i]
-            fix_list, fix_cnt = gate_fix_buffers(lib, u, N) if z is not None else (None, None)
-            args[i] = L.ScanBwdArgs(L.ptr(u), L.ptr(delta), L.ptr(Af), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z),
-                                    L.ptr(bf), L.ptr(dout), L.ptr(fout), L.ptr(state), L.ptr(du), L.ptr(ddelta), L.ptr(dz),
-                                    L.ptr(dA), L.ptr(dBC[0]), L.ptr(dBC[1]), L.ptr(dD), L.ptr(dbias), SB * k, Lq // k,
-                                    split * k, E, N, rl, rh, L.dtype_code(u.dtype), npart, None, None, None, L.ptr(fix_list),
-                                    L.ptr(fix_cnt), L.ptr(dz))
-            args[i].delta_is_dt = int(delta_is_dt)
-            keep.append((dout, dBC, fix_list, fix_cnt))
-            res.append([du, ddelta, dA, dBC, dD, dbias, dz])
-        keep.append(scan_bwd_launch(lib, args, nsets, stream, k, Ps, dirs, split))
+        douts = [d.contiguous() for d in douts]
+        args, res, stream = scan_bwd_sets(lib, [flat[9 * i:9 * i + 9] for i in range(nsets)], z, douts, split, dirs, k=k,
+                                          delta_is_dt=delta_is_dt, gate_fix=gate_fix_buffers)
+        _keep = scan_bwd_launch(lib, args, nsets, stream, k, flat[9 * nsets:], dirs, split)
         if z is not None:  # exact gate gradient at lost gates (z == 0: rare, the launch is a no-op otherwise; fp16: |z| <= 2^-15)
             L.check(lib.cad_scan_bwd_gate_fix(args, nsets, stream), "cad_scan_bwd_gate_fix")
-        grads = []
-        dz_tot = None
-        for i in range(nsets):
-            du, ddelta, dA, dBC, dD, dbias, dz = res[i]
-            u = flat[9 * i]
-            n = dBC[0, 0].numel()
-            npart = dBC.shape[1]
-            dB, dC = torch.empty(dBC.shape[2:], dtype=u.dtype, device=u.device), \
-                torch.empty(dBC.shape[2:], dtype=u.dtype, device=u.device)
-            for src, dst in ((dBC[0], dB), (dBC[1], dC)):
-                L.check(lib.cad_reduce_partials(L.ptr(src), npart, n, L.ptr(dst), L.dtype_code(u.dtype), stream),
-                        "cad_reduce_partials")
-            Adt, Ddt, bdt = pdt[i]
-            grads += [du, ddelta, dA.to(Adt), dB, dC, dD.to(Ddt), dbias.to(bdt)]
-            if dz is not None:
-                dz_tot = dz if dz_tot is None else dz_tot.add_(dz)
-        return (dz_tot, None, None, None, *grads)
+        grads, dz = scan_bwd_grads(res, pdt, stream)
+        return (dz, None, None, None, *[g for set_grads in grads for g in set_grads])
 
 
 def selective_scan_multi(sets, z, split: int, dirs, delta_is_dt: bool = False):
@@ -529,61 +566,38 @@ class _ScanStateful(torch.autograd.Function):
     """One parameter set over a row SEGMENT: (u, delta, A, Bm, Cm, D, z, delta_bias, h0) -> (out, hT).  h0 / hT are the
     (E, SB, N) fp32 states entering / leaving the segment along each row's direction; both are differentiable, so
     consecutive segments chain through plain autograd (chunk-pipelined scans over sequences that do not fit at once, and
-    the building block of caduceus_amd/seqpar.py)."""
+    the building block of caduceus_amd/seqpar.py).  The one-set case of _ScanMulti's path, on the single-set entry points."""
 
     @staticmethod
     def forward(ctx, u, delta, A, Bm, Cm, D, z, bias, h0, split, rev_lo, rev_hi):
         lib = L.get_lib()
-        u, delta, Bm, Cm = u.contiguous(), delta.contiguous(), Bm.contiguous(), Cm.contiguous()
-        z = None if z is None else z.contiguous()
-        E, SB, Lq = u.shape
-        N = A.shape[1]
-        Af, Df, bf = A.float().contiguous(), D.float().contiguous(), bias.float().contiguous()
+        z, (inputs,) = scan_inputs(z, (u, delta, A, Bm, Cm, D, bias))
+        u, delta, Af, Bm, Cm, Df, bf = inputs
+        (E, SB, Lq), N = u.shape, Af.shape[1]
         h0f = None if h0 is None else h0.float().contiguous()
         out = torch.empty_like(u)
         hT = torch.empty((E, SB, N), dtype=torch.float32, device=u.device)
         state = torch.empty((lib.cad_scan_state_floats(E, SB, Lq, N),), dtype=torch.float32, device=u.device)
-        stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, out, state, h0f, hT)
-        a = L.ScanArgs(L.ptr(u), L.ptr(delta), L.ptr(Af), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z), L.ptr(bf), L.ptr(out),
-                       L.ptr(state), SB, Lq, split, E, N, rev_lo, rev_hi, L.dtype_code(u.dtype), L.ptr(h0f), L.ptr(hT), None)
+        a, stream = scan_fwd_args(E, SB, Lq, N, split, (rev_lo, rev_hi), u.dtype, u=u, delta=delta, A=Af, Bm=Bm, Cm=Cm, D=Df, z=z,
+                                  delta_bias=bf, out=out, chunk_state=state, h0=h0f, hT=hT)
         L.check(lib.cad_scan_fwd(C.byref(a), stream), "cad_scan_fwd")
-        ctx.save_for_backward(u, delta, Af, Bm, Cm, Df, z, bf, state, out)
-        ctx.meta = (split, rev_lo, rev_hi, A.dtype, D.dtype, bias.dtype, h0 is not None)
-        ctx.mark_non_differentiable()
+        ctx.save_for_backward(z, *inputs, state, out)
+        ctx.meta = (split, (rev_lo, rev_hi), scan_param_dtypes((u, delta, A, Bm, Cm, D, bias)), h0 is not None)
         return out, hT
 
     @staticmethod
     def backward(ctx, dout, dhT):
         lib = L.get_lib()
-        u, delta, Af, Bm, Cm, Df, z, bf, state, fout = ctx.saved_tensors
-        split, rev_lo, rev_hi, Adt, Ddt, bdt, has_h0 = ctx.meta
-        E, SB, Lq = u.shape
-        N = Af.shape[1]
-        dout = torch.zeros_like(u) if dout is None else dout.contiguous()
+        z, *saved = ctx.saved_tensors
+        split, dirs, pdt, has_h0 = ctx.meta
+        dout = torch.zeros_like(saved[0]) if dout is None else dout.contiguous()
         dhT = None if dhT is None else dhT.float().contiguous()
-        du, ddelta = torch.empty_like(u), torch.empty_like(u)
-        dz = None if z is None else torch.empty_like(u)
-        dA, dD, dbias = torch.zeros_like(Af), torch.zeros_like(Df), torch.zeros_like(bf)
-        npart = lib.cad_scan_bwd_partials(E)
-        dBC = torch.empty((2, npart, N, SB, Lq), dtype=scan_slot_dtype(u.dtype), device=u.device)
-        dh0 = torch.empty((E, SB, N), dtype=torch.float32, device=u.device)
-        stream = L.stream_and_check(u, delta, Af, Bm, Cm, Df, z, bf, dout, state, du, ddelta, dz, dA, dBC, dD, dbias, dhT, dh0)
-        fix_list, fix_cnt = gate_fix_buffers(lib, u, N) if z is not None else (None, None)
-        a = L.ScanBwdArgs(L.ptr(u), L.ptr(delta), L.ptr(Af), L.ptr(Bm), L.ptr(Cm), L.ptr(Df), L.ptr(z), L.ptr(bf),
-                          L.ptr(dout), L.ptr(fout), L.ptr(state), L.ptr(du), L.ptr(ddelta), L.ptr(dz), L.ptr(dA),
-                          L.ptr(dBC[0]), L.ptr(dBC[1]), L.ptr(dD), L.ptr(dbias), SB, Lq, split, E, N, rev_lo, rev_hi,
-                          L.dtype_code(u.dtype), npart, L.ptr(dhT), L.ptr(dh0), None, L.ptr(fix_list), L.ptr(fix_cnt),
-                          L.ptr(dz))
-        L.check(lib.cad_scan_bwd(C.byref(a), stream), "cad_scan_bwd")
+        args, res, stream = scan_bwd_sets(lib, [saved], z, [dout], split, [dirs], dhTs=[dhT], dh0=True, gate_fix=gate_fix_buffers)
+        L.check(lib.cad_scan_bwd(args, stream), "cad_scan_bwd")
         if z is not None:
-            L.check(lib.cad_scan_bwd_gate_fix(C.byref(a), 1, stream), "cad_scan_bwd_gate_fix")
-        n = dBC[0, 0].numel()
-        dB, dC = torch.empty(dBC.shape[2:], dtype=u.dtype, device=u.device), \
-            torch.empty(dBC.shape[2:], dtype=u.dtype, device=u.device)
-        for src, dst in ((dBC[0], dB), (dBC[1], dC)):
-            L.check(lib.cad_reduce_partials(L.ptr(src), npart, n, L.ptr(dst), L.dtype_code(u.dtype), stream),
-                    "cad_reduce_partials")
-        return (du, ddelta, dA.to(Adt), dB, dC, dD.to(Ddt), dz, dbias.to(bdt), dh0 if has_h0 else None, None, None, None)
+            L.check(lib.cad_scan_bwd_gate_fix(args, 1, stream), "cad_scan_bwd_gate_fix")
+        ((du, ddelta, dA, dB, dC, dD, dbias),), dz = scan_bwd_grads(res, pdt, stream)
+        return (du, ddelta, dA, dB, dC, dD, dz, dbias, res[0][0]["dh0"] if has_h0 else None, None, None, None)
 
 
 def selective_scan_stateful(u, delta, A, Bm, Cm, D, z, delta_bias, h0, split: int, rev_lo: int, rev_hi: int):

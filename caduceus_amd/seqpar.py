@@ -128,19 +128,14 @@ class _ScanSeqPar(torch.autograd.Function):
     @staticmethod
     def forward(ctx, group, z, split, dirs, *tensors):
         lib = L.get_lib()
-        nsets = len(tensors) // 7
         rank = dist.get_rank(group)
-        z = None if z is None else z.contiguous()
-        prepared = []
-        for i in range(nsets):
-            u, delta, A, Bm, Cm, D, bias = tensors[7 * i:7 * i + 7]
-            prepared.append((u.contiguous(), delta.contiguous(), A.float().contiguous(), Bm.contiguous(), Cm.contiguous(),
-                             D.float().contiguous(), bias.float().contiguous()))
+        z, prepared = ops.scan_inputs(z, tensors)
+        nsets = len(prepared)
         E, SB, Lq = prepared[0][0].shape
         N = prepared[0][2].shape[1]
         dev, act = prepared[0][0].device, prepared[0][0].dtype
 
-        def launch(h0s, want_state):
+        def launch(h0s):
             args = (L.ScanArgs * nsets)()
             outs, hTs, sdts, states = [], [], [], []
             for i, (u, delta, A, Bm, Cm, D, bias) in enumerate(prepared):
@@ -148,15 +143,15 @@ class _ScanSeqPar(torch.autograd.Function):
                 hT = torch.empty((E, SB, N), dtype=torch.float32, device=dev)
                 sdt = torch.empty((E, SB), dtype=torch.float32, device=dev)
                 state = torch.empty((lib.cad_scan_state_floats(E, SB, Lq, N),), dtype=torch.float32, device=dev)
-                stream = L.stream_and_check(u, delta, A, Bm, Cm, D, z, bias, out, state, hT, sdt, h0s[i] if h0s else None)
-                args[i] = L.ScanArgs(L.ptr(u), L.ptr(delta), L.ptr(A), L.ptr(Bm), L.ptr(Cm), L.ptr(D), L.ptr(z),
-                                     L.ptr(bias), L.ptr(out), L.ptr(state), SB, Lq, split, E, N, dirs[i][0], dirs[i][1],
-                                     L.dtype_code(act), L.ptr(h0s[i]) if h0s else None, L.ptr(hT), L.ptr(sdt))
+                args[i], stream = ops.scan_fwd_args(E, SB, Lq, N, split, dirs[i], act, u=u, delta=delta, A=A, Bm=Bm, Cm=Cm, D=D, z=z,
+                                                    delta_bias=bias, out=out, chunk_state=state, hT=hT, sum_dt=sdt,
+                                                    h0=h0s[i] if h0s else None)
                 outs.append(out), hTs.append(hT), sdts.append(sdt), states.append(state)
             L.check(lib.cad_scan_fwd_multi(args, nsets, stream), "cad_scan_fwd_multi")
             return outs, hTs, sdts, states
 
-        _, hT_loc, sdt_loc, _ = launch(None, False)  # pass 1: segment from a zero state -> its affine map
+        # pass 1: segment from a zero state -> its affine map (known gap: a full pass, not the map_only mode of ops.scan_fwd_launch)
+        _, hT_loc, sdt_loc, _ = launch(None)
         h0s, Ps = [], []
         for i in range(nsets):
             S_all = _all_gather(hT_loc[i], group)
@@ -165,9 +160,8 @@ class _ScanSeqPar(torch.autograd.Function):
             P_all = [torch.exp(A.unsqueeze(1) * sd.unsqueeze(-1)) for sd in sdt_all]  # (E, SB, N) each
             h0s.append(_compose(P_all, S_all, rank, split, dirs[i][0], dirs[i][1], towards_end=False).contiguous())
             Ps.append(torch.stack(P_all))
-        outs, _, _, states = launch(h0s, True)       # pass 2: from the true entry state
-        ctx.group, ctx.meta = group, (split, dirs, nsets, [(t[2].dtype, t[5].dtype, t[6].dtype) for t in
-                                                      [tensors[7 * i:7 * i + 7] for i in range(nsets)]])
+        outs, _, _, states = launch(h0s)             # pass 2: from the true entry state
+        ctx.group, ctx.meta = group, (split, dirs, nsets, ops.scan_param_dtypes(tensors))
         flat = []
         for i in range(nsets):
             flat += [*prepared[i], states[i], outs[i], Ps[i]]
@@ -181,53 +175,26 @@ class _ScanSeqPar(torch.autograd.Function):
         group = ctx.group
         split, dirs, nsets, pdt = ctx.meta
         rank = dist.get_rank(group)
-        sets = [flat[10 * i:10 * i + 10] for i in range(nsets)]
-        E, SB, Lq = sets[0][0].shape
-        N = sets[0][2].shape[1]
-        dev, act = sets[0][0].device, sets[0][0].dtype
-        npart = lib.cad_scan_bwd_partials(E)
+        sets = [flat[10 * i:10 * i + 9] for i in range(nsets)]
+        npart = lib.cad_scan_bwd_partials(sets[0][0].shape[0])
         douts = [d.contiguous() for d in douts]
 
         def launch(dhTs):
-            args = (L.ScanBwdArgs * nsets)()
-            res = []
-            for i, (u, delta, A, Bm, Cm, D, bias, state, fout, _P) in enumerate(sets):
-                du, ddelta = torch.empty_like(u), torch.empty_like(u)
-                dz = None if z is None else torch.empty_like(u)
-                dA, dD, dbias = torch.zeros_like(A), torch.zeros_like(D), torch.zeros_like(bias)
-                dBC = torch.empty((2, npart, N, SB, Lq), dtype=act, device=dev)
-                dh0 = torch.empty((E, SB, N), dtype=torch.float32, device=dev)
-                stream = L.stream_and_check(u, delta, A, Bm, Cm, D, z, bias, douts[i], state, du, ddelta, dz, dA, dBC, dD,
-                                            dbias, dh0, dhTs[i] if dhTs else None)
-                args[i] = L.ScanBwdArgs(L.ptr(u), L.ptr(delta), L.ptr(A), L.ptr(Bm), L.ptr(Cm), L.ptr(D), L.ptr(z),
-                                        L.ptr(bias), L.ptr(douts[i]), L.ptr(fout), L.ptr(state), L.ptr(du), L.ptr(ddelta),
-                                        L.ptr(dz), L.ptr(dA), L.ptr(dBC[0]), L.ptr(dBC[1]), L.ptr(dD), L.ptr(dbias), SB, Lq,
-                                        split, E, N, dirs[i][0], dirs[i][1], L.dtype_code(act), npart,
-                                        L.ptr(dhTs[i]) if dhTs else None, L.ptr(dh0))
-                res.append([du, ddelta, dA, dBC, dD, dbias, dz, dh0])
+            # gate_fix=None is a known gap: no worklist, and no cad_scan_bwd_gate_fix behind the scan (lost gates keep the plain gradient)
+            args, res, stream = ops.scan_bwd_sets(lib, sets, z, douts, split, dirs, npart=npart, dhTs=dhTs, dh0=True, gate_fix=None)
             L.check(lib.cad_scan_bwd_multi(args, nsets, stream), "cad_scan_bwd_multi")
             return res, stream
 
-        first, _ = launch(None)  # pass 1: state-gradient map of the segment (zero gradient entering from the far side)
+        # pass 1: state-gradient map of the segment, zero gradient entering from the far side (known gap: a full pass, not carry_only)
+        first, _ = launch(None)
         dhTs = []
         for i in range(nsets):
-            G_all = _all_gather(first[i][7], group)
-            P_all = list(sets[i][9].unbind(0))
+            G_all = _all_gather(first[i][0]["dh0"], group)
+            P_all = list(flat[10 * i + 9].unbind(0))
             dhTs.append(_compose(P_all, G_all, rank, split, dirs[i][0], dirs[i][1], towards_end=True).contiguous())
         res, stream = launch(dhTs)
-        grads, dz_tot = [], None
-        for i in range(nsets):
-            du, ddelta, dA, dBC, dD, dbias, dz, _ = res[i]
-            n = dBC[0, 0].numel()
-            dB, dC = torch.empty(dBC.shape[2:], dtype=act, device=dev), torch.empty(dBC.shape[2:], dtype=act, device=dev)
-            for src, dst in ((dBC[0], dB), (dBC[1], dC)):
-                L.check(lib.cad_reduce_partials(L.ptr(src), npart, n, L.ptr(dst), L.dtype_code(act), stream),
-                        "cad_reduce_partials")
-            Adt, Ddt, bdt = pdt[i]
-            grads += [du, ddelta, dA.to(Adt), dB, dC, dD.to(Ddt), dbias.to(bdt)]
-            if dz is not None:
-                dz_tot = dz if dz_tot is None else dz_tot + dz
-        return (None, dz_tot, None, None, *grads)
+        grads, dz = ops.scan_bwd_grads(res, pdt, stream, dz_in_place=False)
+        return (None, dz, None, None, *[g for set_grads in grads for g in set_grads])
 
 
 def selective_scan_multi(sets, z, split: int, dirs):

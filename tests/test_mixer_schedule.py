@@ -64,6 +64,17 @@ SCHEDULE = {
     cad_proj_wx_wgrad_supported cad_proj_wx_wgrad cad_proj_wgrad_only_supported cad_proj_wx_wgrad cad_proj_wx_supported cad_proj_wx
     cad_conv1d_bwd_slots cad_conv1d_bwd_slots cad_conv1d_bwd_multi_slotted cad_gemm_stream_supported cad_gemm_stream cad_gemm_stream_supported
     cad_gemm_stream cad_fold_f32_multi""",
+    "scan_multi_k1": """
+    cad_scan_chunk_len cad_scan_state_floats cad_scan_chunk_len cad_scan_state_floats cad_scan_fwd_multi cad_scan_bwd_partials
+    cad_scan_gate_fix_entries cad_scan_bwd_partials cad_scan_gate_fix_entries cad_scan_bwd_multi cad_scan_bwd_gate_fix cad_reduce_partials
+    cad_reduce_partials cad_reduce_partials cad_reduce_partials""",
+    "scan_multi_k2": """
+    cad_scan_chunk_len cad_scan_state_floats cad_scan_chunk_len cad_scan_state_floats cad_scan_fwd_multi cad_scan_fwd_multi
+    cad_scan_bwd_partials cad_scan_gate_fix_entries cad_scan_bwd_partials cad_scan_gate_fix_entries cad_scan_bwd_multi cad_scan_bwd_multi
+    cad_scan_bwd_gate_fix cad_reduce_partials cad_reduce_partials cad_reduce_partials cad_reduce_partials""",
+    "scan_stateful": """
+    cad_scan_state_floats cad_scan_fwd cad_scan_bwd_partials cad_scan_gate_fix_entries cad_scan_bwd cad_scan_bwd_gate_fix
+    cad_reduce_partials cad_reduce_partials""",
 }
 
 
@@ -121,6 +132,44 @@ def test_mixer_layer_schedule(backend, case, d_model, L, dtype, cache):
     halves, the chunked dW_x) and fp32 (cad_gemm_f32 throughout, the fold kernel behind the scan)."""
     name, dev = backend
     _check(_recorded_layer(dev, d_model, L, dtype, cache), SCHEDULE[case])
+
+
+def _recorded_scan(dev, stateful):
+    """The cad_* calls of one autograd scan, forward + backward in bf16: two sets under a shared gate (ops.selective_scan_multi), or one
+    segment entered through h0 whose hT the loss uses (ops.selective_scan_stateful)."""
+    E, SB, N, Lq = 16, 2, 16, 4 * int(_lib.get_lib().cad_scan_chunk_len())
+    torch.manual_seed(0)
+    rand = lambda *shape: (torch.randn(*shape, device=dev) * 0.5).to(torch.bfloat16).requires_grad_(True)
+    sets = [(rand(E, SB, Lq), rand(E, SB, Lq), (-torch.rand(E, N, device=dev) - 0.5).requires_grad_(True), rand(N, SB, Lq), rand(N, SB, Lq),
+             torch.randn(E, device=dev, requires_grad=True), torch.randn(E, device=dev, requires_grad=True)) for _ in range(2)]
+    z, h0 = rand(E, SB, Lq), torch.randn(E, SB, N, device=dev, requires_grad=True)
+    real, calls = _lib.get_lib(), []
+    _lib._lib = _Recorder(real, calls)
+    try:
+        if stateful:
+            u, delta, A, Bm, Cm, D, bias = sets[0]
+            out, hT = ops.selective_scan_stateful(u, delta, A, Bm, Cm, D, z, bias, h0, 1, 0, 1)
+            (out.float().sum() + hT.sum()).backward()
+        else:
+            y_f, y_r = ops.selective_scan_multi(sets, z, 1, [(0, 1), (1, 0)])
+            (y_f.float().sum() + y_r.float().sum()).backward()
+    finally:
+        _lib._lib = real
+    used = [z, *sets[0], *(sets[1] if not stateful else (h0,))]
+    assert all(t.grad is not None for t in used)
+    return calls
+
+
+@pytest.mark.parametrize("case,lsplit", [("scan_multi_k1", None), ("scan_multi_k2", "2"), ("scan_stateful", None)])
+def test_autograd_scan_schedule(backend, monkeypatch, case, lsplit):
+    """The scans outside the mixer (ops.py), lists recorded at the commit BEFORE their argument structs and backward moved into shared
+    helpers: one launch per pass, one gate fix, two folds per set; k = 2 adds the map / carry passes of the L-split."""
+    name, dev = backend
+    if lsplit is None:
+        monkeypatch.delenv("CADUCEUS_AMD_LSPLIT", raising=False)
+    else:
+        monkeypatch.setenv("CADUCEUS_AMD_LSPLIT", lsplit)
+    _check(_recorded_scan(dev, case == "scan_stateful"), SCHEDULE[case])
 
 
 def test_mixer_layer_schedule_with_the_concurrent_fold(backend, monkeypatch):
