@@ -219,9 +219,7 @@ __device__ __forceinline__ int cad_cu_key() {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     return (int)(((xcc & 15u) << 8) | ((hw >> 8) & 255u));
 }
-#ifndef CAD_POLL_SLEEP
 #define CAD_POLL_SLEEP 32
-#endif
 __device__ __forceinline__ void cad_poll_sleep() { __builtin_amdgcn_s_sleep(CAD_POLL_SLEEP); }  // 64 cycles per unit
 __device__ __forceinline__ uint64_t cad_wall_clock() { return wall_clock64(); }             // constant-rate counter
 #define CAD_WALL_CLOCK_TICKS_PER_US 100ull  /* the wall clock of the device side runs at 100 MHz */

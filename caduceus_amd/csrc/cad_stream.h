@@ -7,9 +7,7 @@
 #pragma once
 #include "cad_common.h"
 
-#ifndef CAD_NT_MASK
 #define CAD_NT_MASK 7
-#endif
 #define CAD_STREAM_PROJ 0
 #define CAD_STREAM_CONV 1
 #define CAD_STREAM_NORM 2

@@ -24,9 +24,7 @@ namespace {
 #define CV_TILES_BWD 8                            // wave tiles a backward workgroup walks before reducing dw / dbias
 #define CV_TILES_FWD 4                            // wave tiles a forward wave walks (the next tile's load in flight under the arithmetic)
 #define CV_MAXSETS 2
-#ifndef CV_BWD_WAVES
 #define CV_BWD_WAVES 4                            // waves per SIMD the backward is compiled for (<= 128 VGPRs)
-#endif
 
 struct ConvFwdSets {
     cad_conv1d_args s[CV_MAXSETS];

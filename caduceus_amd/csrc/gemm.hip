@@ -35,15 +35,9 @@ __device__ __forceinline__ float gp_softplus(float x) {
 }
 
 // K = 512 (d_model 512, configs[4]) tuning knobs: W rows per wave / tokens per block / register double-buffering of the A fragments
-#ifndef GP_MB16
 #define GP_MB16 2
-#endif
-#ifndef GP_NT16
 #define GP_NT16 32
-#endif
-#ifndef GP_XFB16
 #define GP_XFB16 1
-#endif
 template <int KS>
 struct GpCfg {
     static constexpr int MB = KS >= 16 ? GP_MB16 : 4;  // 16-row blocks of W per wave: MB * KS * 4 <= 128 VGPRs
@@ -668,16 +662,10 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
 // cad_proj_wx's thin kernel (same swizzle, same counted waits).  MFMA roles: A = W fragment (rows = output features), B = X fragment
 // by transposing reads (columns = tokens), so a D lane holds FOUR CONSECUTIVE FEATURES of one token = 8 contiguous bytes of the
 // token-major output; fp32 accumulation over both panels and all of K, one rounding to bf16.
-#ifndef GP_XTW_PLAIN_STORES
-#define GP_XTW_PLAIN_STORES 1   // ordinary stores: the 8-byte pieces of a token row meet in L2 (streaming stores of partial lines: 0.277 vs 0.212 ms)
-#endif
-#ifndef GP_XTW_RING
+// The output leaves with ordinary stores: the 8-byte pieces of a token row meet in L2 (streaming stores of partial lines measured 0.277
+// vs 0.212 ms, profiles/r04_out_proj.txt).
 #define GP_XTW_RING 4           // LDS tiles of the X ring: RING - 1 chunks (16 KB each) in flight per CU (8 slots measured SLOWER:
                                // 0.222 vs 0.206 ms, profiles/r04_out_proj.txt)
-#endif
-#ifndef GP_XTW_KS_OUTER
-#define GP_XTW_KS_OUTER 1
-#endif
 template <typename TE, int MB, int KS>
 __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_args a) {
     typedef GtCfg C;
@@ -761,10 +749,9 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
                 slot = (slot + 1) & (XR - 1);
                 // (k step outer, token sub-block inner: consecutive MFMAs go to sixteen different accumulator tiles)
 #pragma unroll
-                for (int o1 = 0; o1 < (GP_XTW_KS_OUTER ? C::KC / 32 : C::NT / 16); ++o1) {
+                for (int ks = 0; ks < C::KC / 32; ++ks) {
 #pragma unroll
-                    for (int o2 = 0; o2 < (GP_XTW_KS_OUTER ? C::NT / 16 : C::KC / 32); ++o2) {
-                        const int ks = GP_XTW_KS_OUTER ? o1 : o2, q = GP_XTW_KS_OUTER ? o2 : o1;
+                    for (int q = 0; q < C::NT / 16; ++q) {
                         const int r0 = ks * 32 + g * 8 + (jl >> 2);
                         const char* p0 = xt + r0 * C::XROW + ((q ^ gx_swz(r0)) * 32) + (jl & 3) * 8;
                         const char* p1 = xt + (r0 + 4) * C::XROW + ((q ^ gx_swz(r0 + 4)) * 32) + (jl & 3) * 8;
@@ -788,13 +775,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
                 pk[1] = cad_pack2_safe<TE>(d[q][mb][2], d[q][mb][3]);
                 // (every lane issues the store: the counted waits above rely on exactly NST store instructions per block; lanes of a tail
                 // block / beyond M are masked off by the exec mask, the instruction still counts)
-                if (t < T && m + 4 <= M) {
-#if GP_XTW_PLAIN_STORES
-                    *(u32x2*)(out + t * a.ldo + m) = pk;
-#else
-                    cad_store_stream<CAD_STREAM_PROJ>((u32x2*)(out + t * a.ldo + m), pk);
-#endif
-                }
+                if (t < T && m + 4 <= M) *(u32x2*)(out + t * a.ldo + m) = pk;
             }
         }
         // (a block with masked-off store instructions -- the tail block, or a wave beyond M -- issued an unknown number of them: the
@@ -811,32 +792,16 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
 // and 4 B fragments through the transposing read (B rows are k, columns contiguous) and issues 32 MFMAs.  Both operands cross HBM
 // once per tile row / column they belong to: the kernel is the classic tiled GEMM, written for the three shapes of the mixer
 // backward where R or C is only one or four tiles wide and everything else is the stream.
-#ifndef GS_SLICE_INTERLEAVE
-#define GS_SLICE_INTERLEAVE 0   // measured: 0.303 vs 0.249 ms (neighbouring workgroups on neighbouring 64-byte pieces is WORSE)
-#endif
-#ifndef GS_SLICE_ROTATE
-#define GS_SLICE_ROTATE 1
-#endif
+// Weight-gradient mode (nslices > 1): every (slice, row tile) starts its walk at a different chunk of its contiguous k range and wraps around,
 // start chunk of (slice sl, row tile rt) = (2 sl + rt) mod chunks-per-slice: the 64 x 4 workgroups of a configs[2] weight gradient then
 // sit on all 128 chunk phases of the 8 KB every slice owns in a strided row at once.  tools/gemm_stream_bench.py, same box, ms per
 // product (library K-split bmm + sum: 0.232): no rotation 0.249 | (37, 11) 0.232 | (53, 29) 0.243 | (19, 5) 0.232 | (45, 77) 0.243 |
 // (27, 32) 0.250 | (64, 16) 0.255 | (1, 32) 0.255 | (3, 1) 0.226 | (3, 64) 0.228 | (1, 0) 0.225 | (4, 1) 0.231 | (5, 2) 0.233 |
-// (7, 3) 0.222 | (2, 1) 0.215 -- and neighbouring workgroups on neighbouring 64-byte pieces (GS_SLICE_INTERLEAVE) 0.303.
-#ifndef GS_XCD_REMAP
-#define GS_XCD_REMAP 1
-#endif
-// timing experiments only (WRONG results; the library says TIMING-BUILD): 1 = no fragment reads / MFMAs (what do the two operand streams,
-// the barriers and the stores cost alone), 2 = no LDS-DMA (what does the multiplication cost alone), 4 = MFMAs on constant fragments (no
-// LDS fragment reads).  tools/gemm_stream_bench.py over -DGS_WHATIF=... builds; profiles/r06_gemm_stream_whatif.txt
-#ifndef GS_WHATIF
-#define GS_WHATIF 0
-#endif
-#ifndef GS_ROT_SL
+// (7, 3) 0.222 | (2, 1) 0.215 -- and slices interleaved chunk by chunk (neighbouring workgroups on neighbouring 64-byte pieces) 0.303.
+// (What binds the kernel -- operand streams, fragment reads or the multiplication -- was answered with timing builds of it:
+// profiles/r06_gemm_stream_whatif.txt.)
 #define GS_ROT_SL 2
-#endif
-#ifndef GS_ROT_RT
 #define GS_ROT_RT 1
-#endif
 struct GsCfg {
     static constexpr int RT = 256, CT = 256, KC = 32, RING = 4;
     static constexpr int AROW = KC * 2;               // 64 bytes per A tile row: four 16-byte pieces, piece index ^ gs_aswz(row)
@@ -889,7 +854,7 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
     // of operands at the configs[2] weight gradient = B four times).  Workgroup b therefore takes item (b % 8) (grid / 8) + b / 8: every XCD
     // owns a contiguous run of items, the sharers meet in one L2.
     const int64_t istep = gridDim.x;
-    const int64_t i0 = (GS_XCD_REMAP && (gridDim.x % 8) == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
+    const int64_t i0 = (gridDim.x % 8) == 0 ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
     if (i0 >= nitems) return;
     const int64_t nmine = (nitems - i0 + istep - 1) / istep;
     const int64_t total = nmine * nk;
@@ -912,27 +877,23 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
     int ich = 0, islot = 0;
     int64_t iitem = i0;
     const TE *iA = nullptr, *iB = nullptr;
-    // GS_SLICE_INTERLEAVE (weight-gradient mode, nslices > 1): slice s takes the 32-k chunks s, s + nslices, s + 2 nslices, ... of the
-    // reduction range instead of one contiguous k range, so that the workgroups running side by side read NEIGHBOURING 64-byte pieces of
-    // the same strided rows (one DRAM page serves them all) instead of 64 bytes each from pages 8 KB apart
-    const int64_t kstep = (GS_SLICE_INTERLEAVE && a.nslices > 1) ? (int64_t)a.nslices * C::KC : (int64_t)C::KC;
-    // GS_SLICE_ROTATE (weight-gradient mode): every (slice, row tile) starts its walk at a different chunk of its k range and wraps
-    // around.  The slices are 8 KB apart in every strided row and all workgroups advance in step, so without the rotation the whole
-    // chip reads the same 4 KB phase of every 8 KB at any moment (the order of a slice's chunks only changes fp32 rounding).
+    // Weight-gradient mode: every (slice, row tile) starts its walk at a different chunk of its k range and wraps around.  The slices
+    // are 8 KB apart in every strided row and all workgroups advance in step, so without the rotation the whole chip reads the same
+    // 4 KB phase of every 8 KB at any moment (the order of a slice's chunks only changes fp32 rounding).
     int irot = 0;
     auto seek = [&]() {
         int64_t rt, ct, sl;
         decode(iitem, rt, ct, sl);
-        const int64_t kbase = (GS_SLICE_INTERLEAVE && a.nslices > 1) ? sl * C::KC : sl * kper;
+        const int64_t kbase = sl * kper;
         iA = (const TE*)a.A + rt * C::RT * a.lda + kbase;
         iB = (const TE*)a.B + kbase * a.ldb + ct * C::CT;
-        irot = (GS_SLICE_ROTATE && a.nslices > 1) ? (int)((sl * GS_ROT_SL + rt * GS_ROT_RT) % nk) : 0;
+        irot = a.nslices > 1 ? (int)((sl * GS_ROT_SL + rt * GS_ROT_RT) % nk) : 0;
     };
     seek();
     auto issue_next = [&]() {
         int kc = ich + irot;
         if (kc >= nk) kc -= nk;
-        if (!(GS_WHATIF & 2)) gs_issue_chunk(iA, a.lda, iB, a.ldb, (int64_t)kc * kstep, smem + islot * C::STAGE, wave, lane);
+        gs_issue_chunk(iA, a.lda, iB, a.ldb, (int64_t)kc * C::KC, smem + islot * C::STAGE, wave, lane);
         islot = (islot + 1) & (C::RING - 1);
         if (++ich == nk) {
             ich = 0;
@@ -973,22 +934,16 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void gemm_stream_kernel(cad_gemm_
             if (it + C::RING - 1 < total) issue_next();
             const char* st = smem + slot * C::STAGE;
             slot = (slot + 1) & (C::RING - 1);
-            if (GS_WHATIF & 1) continue;
             u32x4 bfr[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (GS_WHATIF & 4) {
-                    bfr[j] = u32x4{(uint32_t)(lane + j), (uint32_t)it, 0x3f803f80u, (uint32_t)slot};
-                    continue;
-                }
                 const u32x2 lo = cad_lds_read_tr16(st + b_off0 + ((j ^ bs0) * 32));
                 const u32x2 hi = cad_lds_read_tr16(st + b_off1 + ((j ^ bs1) * 32));
                 bfr[j] = u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const u32x4 af = (GS_WHATIF & 4) ? u32x4{(uint32_t)(lane ^ i), 0x3f803f80u, (uint32_t)it, 0u}
-                                                  : *(const u32x4*)(st + a_off + i * 16 * C::AROW);
+                const u32x4 af = *(const u32x4*)(st + a_off + i * 16 * C::AROW);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = cad_mfma_16x16x32<TE>(af, bfr[j], acc[i][j]);
             }

@@ -11,16 +11,16 @@
 // dB / dC must be summed over all E channels.  Measured on MI355X (profiles/r01_scan_v2_pmc_summary.txt and the
 // microbenchmarks next to it): a global fp32 atomic costs one un-coalesced 64-byte HBM write per LANE, and an LDS
 // ds_add_f32 retires only ~1 lane every 3 cycles (~200 cycles per wave instruction) -- so NO atomics of either kind are
-// used.  Each of the SC_W_BWD waves (channels) of a workgroup writes its dB/dC contributions with plain ds_write_b64
-// into its own region of a double-buffered LDS slab; after the (single) barrier of the pair the 512 threads sum the
-// SC_W_BWD regions and store the workgroup's partial sums with coalesced 16-byte stores to slot blockIdx.x of a
-// (E / SC_W_BWD)-deep partial buffer; cad_reduce_partials folds the slots (and converts to the activation dtype) in a
-// second, purely streaming pass.
+// used.  Each of the SC_W_BWD waves (channels) of a workgroup writes its dB/dC contributions into its own region of a
+// double-buffered LDS slab (one barrier per pair-step); the regions are then summed and the workgroup's partial sums
+// stored to slot blockIdx.x of a (E / SC_W_BWD)-deep partial buffer.  bf16: the slab holds packed bf16x2 dwords, the
+// staging waves 0-3 sum the eight regions on the matrix core and store 16 bytes per lane write-through (see PK_TILE);
+// fp32 / fp16: fp32 slab, every thread sums its positions over the regions.  The slots are folded (and converted to the
+// activation dtype) by scan_fold.hip: after the launch (cad_reduce_partials) or chunk by chunk while it runs
+// (cad_fold_partials_stream, which follows the arrivals published per (row, chunk) below).
+// Closed alternatives (one slab buffer, 4-wave workgroups, a swizzled slab, the flush on the other waves, plain slot stores, register
+// instead of LDS-DMA prefetch on the packed path, the round-4 prologue) live in profiles/ and in git, not behind switches here.
 #include "scan_common.h"
-
-#ifndef SC_PRE_WAIT
-#define SC_PRE_WAIT 0   // 1: counted wait at the chunk start (leaves the most recent stores in flight)
-#endif
 
 namespace {
 
@@ -36,7 +36,7 @@ struct ScanBwdSets {
                                         // (items i and i + 4 of neighbouring lanes) fall into different LDS banks
 #define ACC_TILE (SC_S * ACC_ISTR)      // floats per (wave, tensor) region, layout [item i][lane j][state s]
 #define ACC_BUF (SC_W * 2 * ACC_TILE)  // floats per buffer: [wave][dB,dC][ACC_TILE]
-// bf16 kernels (8-wave workgroups) keep the slab as packed bf16x2 dwords -- one dword = both states of one position.
+// bf16 kernels keep the slab as packed bf16x2 dwords -- one dword = both states of one position.
 // Region of one (channel = wave, tensor): [q = item-pair block 0/1][lane 64][4 dwords = items 4q .. 4q+3], i.e. a lane's
 // four items of block q form one 16-byte PIECE.  The contributions are rounded to bf16 before the 8-channel sum; the
 // partial slots they are summed into are bf16 anyway (same error order).
@@ -46,26 +46,13 @@ struct ScanBwdSets {
 // the rows as (state 0: items 0..3, state 1: items 0..3), which leaves every D lane with four consecutive positions of
 // one state row.  One wave owns the two tiles (q = 0, 1) of (tensor, 16-lane block): 4 ds_read_b128 + 4 MFMA + 4
 // v_cvt_pk + one 16-byte store per pair-step instead of 8 ds_read_b64 + ~64 VALU + 2 stores per thread.
-#ifndef SC_SLAB_PACKED
-#define SC_SLAB_PACKED 1
-#endif
 #define PK_Q (64 * 4)                   // dwords per item-pair block
 #define PK_TILE (2 * PK_Q)              // dwords per (wave, tensor) region (2 KB: a multiple of the 256-byte bank row, so
                                         // the ds_read_b128 of the four channel groups are conflict-free)
 #define PK_BUF (SC_W * 2 * PK_TILE)     // dwords per buffer
-// LDS-DMA prefetch of the next chunk's item vectors (bf16 production kernel): 6 vectors x SC_W waves x 64 lanes x 16 bytes
-#ifndef SC_BWD_SLAB_SWZ
-#define SC_BWD_SLAB_SWZ 0  // 1: exchange the item pairs of a slab piece on lanes 8..15 of every 16 (no bank conflicts on the slab
-                           // writes; measured 1.5 % SLOWER: the 8 selects after the MFMA cost more than the conflicts, which hide)
-#endif
-#ifndef SC_BWD_PREFETCH
-#define SC_BWD_PREFETCH 1
-#endif
+// LDS-DMA prefetch of the next chunk's item vectors (bf16 vector kernels): 6 vectors x SC_W waves x 64 lanes x 16 bytes
 #define PRE_SLOT (SC_W * 64 * 16)       // bytes per vector slot (all waves)
 #define PRE_BYTES (SC_NDMA * PRE_SLOT)
-#ifndef SC_SLAB_BUFS
-#define SC_SLAB_BUFS 2                  // 2: one barrier per pair; 1: half the LDS (two workgroups per CU), two barriers
-#endif
 
 static_assert(SC_CHUNK == SC_STATE_STEP, "backward chunk = one saved-state slot");
 // Only S = 8 items per lane is a supported backward.  S = 4 (a 128-VGPR build: four waves per SIMD) was asked for as an experiment
@@ -75,35 +62,19 @@ static_assert(SC_CHUNK == SC_STATE_STEP, "backward chunk = one saved-state slot"
 // segment, pair), so halving the segment doubles ~40 % of the instructions per element (the forward built that way measured -15 %,
 // profiles/r03_occupancy_experiments.txt); (iii) the packed slab / MFMA flush / 16-byte LDS-DMA vectors are laid out for 8 items.
 static_assert(SC_S_BWD == 8, "the backward scan is written for 8 items per lane (see the comment above)");
-// SC_BWD_UNROLL_NP = 8: the production instantiation (bf16, vector path, d_state = 16) has its pair loop fully unrolled -- the pair
+// Eight waves per workgroup: staging needs >= 256 threads, and the MFMA flush sums two groups of four channels.  Two 4-wave workgroups per
+// CU were built and measured 15 % slower (profiles/r06_ab_w4_workgroups.txt).
+static_assert(SC_W == 8, "the backward scan is written for 8 waves per workgroup");
+// The production instantiation (bf16, vector path, d_state = 16 = SC_BWD_UNROLL_NP pairs) has its pair loop fully unrolled -- the pair
 // index is a compile-time constant, so lane selections become immediates and the tile-buffer parity and the `more` / staging
 // conditions fold: 3.93 -> 3.80 ms per two-set launch in a same-box A/B (profiles/r04_scan_bwd_floor_and_unroll.txt; 244 VGPRs, no
-// scratch).  Every other shape runs the generic instantiation (NPC = 0: run-time pair count).  -DSC_BWD_UNROLL_NP=0: round-3 kernel.
-#ifndef SC_BWD_UNROLL_NP
+// scratch).  Every other shape runs the generic instantiation (NPC = 0: run-time pair count).
 #define SC_BWD_UNROLL_NP 8
-#endif
-#ifndef SC_BWD_FLUSH_HALF
-#define SC_BWD_FLUSH_HALF 1   // which waves run the MFMA flush of a pair-step's dB / dC slab: 1 = the staging waves 0-3 (both tensors of their
-                              // lane block), 0 = all eight (one tile pair each), 2 = waves 4-7
-#endif
-#ifndef SC_BWD_LEAN
-#define SC_BWD_LEAN 1   // 0: the round-4 prologue / epilogue / per-pair-step dA wave sum for every launch (A/B switch)
-#endif
-static_assert(SC_W == 4 || SC_W == 8, "staging needs >= 256 threads; the flush mapping is written for 256 / 512");
 
-// The dB / dC partial-slot stores of the production (packed, vector) kernel: write-through (sc1), which is what lets a fold kernel on
-// another stream read them while this launch still runs -- and they are never read again by THIS kernel, so nothing is lost when the
-// line leaves the XCD's L2.  -DSC_BWD_SLOT_WT=0: plain stores (A/B switch; the concurrent fold then must not be used).
-#ifndef SC_BWD_SLOT_WT
-#define SC_BWD_SLOT_WT 1
-#endif
-__device__ __forceinline__ void sc_slot_store16(void* p, u32x4 v) {
-#if SC_BWD_SLOT_WT
-    cad_store16_wt(p, v);
-#else
-    *(u32x4*)p = v;
-#endif
-}
+// The dB / dC partial-slot stores of the packed (bf16) kernels: write-through (sc1), which is what lets a fold kernel on another stream
+// read them while this launch still runs -- and they are never read again by THIS kernel, so nothing is lost when the line leaves the
+// XCD's L2.
+__device__ __forceinline__ void sc_slot_store16(void* p, u32x4 v) { cad_store16_wt(p, v); }
 
 // The gate gradient recovers  y sigmoid(z) = out / z  from the STORED output.  A gate is LOST where that quotient cannot be formed:
 //   * fp32 / bf16: |z| < 2^-100 -- z == 0 (out == 0), and the smallest gates, whose 1 / z leaves fp32's range (0 * inf, or inf).  At
@@ -154,11 +125,10 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
     constexpr int TILE = SC_TILE(SC_S), ROW = SC_ROW(SC_S);
     const cad_scan_bwd_args& a = sets.s[blockIdx.z];
     float* acc = smem + 4 * TILE;
-    constexpr bool PACKED = SC_SLAB_PACKED && cad_is_bf16<T>::value && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;  // (bf16 MFMA flush)
+    constexpr bool PACKED = cad_is_bf16<T>::value;  // (packed slab, MFMA flush)
     uint32_t* accp = (uint32_t*)acc;
-    static_assert(!PACKED || SC_S == 8, "packed slab: two 4-item blocks per lane");
     // item vectors of the next chunk travel global -> LDS by DMA one chunk ahead (16-byte vectors: bf16, 8 items)
-    constexpr bool PREF = SC_BWD_PREFETCH && PACKED && VEC && SC_S * sizeof(T) == 16;
+    constexpr bool PREF = PACKED && VEC;
     // [vector 0..5][wave][lane][16 bytes], behind the two slab buffers (a carry-only pass has no slab: 68 KB of LDS in all, so two
     // of its workgroups -- 92 VGPRs -- share a CU)
     char* pre = CO ? (char*)acc : (char*)(accp + 2 * PK_BUF);
@@ -173,7 +143,6 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
         selA[2] = (lane & 3) == 2 ? one : 0u, selA[3] = (lane & 3) == 3 ? one : 0u;
     }
     const int wave = cad_uniform(threadIdx.x >> 6);
-    sc_static_priority(wave, SC_W);
     const int64_t sb = blockIdx.y;
     const int e_raw = blockIdx.x * SC_W + wave;
     const bool act = e_raw < a.E;
@@ -283,7 +252,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
         float sum_dt = 0.f;    // sum of dt over the lane's items: prod_i a_i = exp2(A2 * sum_dt)
         // (publishing: every wave's slot stores of the previous chunk must have completed before the barrier of pair-step 0 -- the
         // prefetching instantiations wait for vmcnt(0) here anyway, for their item vectors)
-        if constexpr (!PREF || SC_PRE_WAIT) {
+        if constexpr (!PREF) {
             if (pub) cad_wait_vmcnt<0>();
         }
         if constexpr (LEAN) {
@@ -292,7 +261,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
             // dA term = t * 0, d(delta) = (..) * (1 - exp(-0))), so ONLY these two vectors are masked -- the clamped prefetch address
             // delivers finite data of the row start for the others -- and no per-item select is left.  dy = 0 also silences a padding
             // wave (E % SC_W != 0: its state-gradient carry starts from 0, so g stays 0).
-            sc_wait_loads<SC_PRE_WAIT ? 3 : 0>();
+            sc_wait_loads<0>();
             const char* slot = pre + wave * (64 * 16) + lane * 16;
             typedef ScVec<T, SC_S> V;
             const uint32_t inm = p0 < L ? 0xffffffffu : 0u, livem = (p0 < L && act) ? 0xffffffffu : 0u;
@@ -310,7 +279,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
             if (o2_row) o2_raw = rd_raw(5);
         } else if constexpr (PREF) {
             // this chunk's vectors were fetched into LDS one chunk ago
-            sc_wait_loads<SC_PRE_WAIT ? 3 : 0>();
+            sc_wait_loads<0>();
             const char* slot = pre + wave * (64 * 16) + lane * 16;
             const bool in = p0 < L;
             typedef ScVec<T, SC_S> V;
@@ -517,9 +486,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
             }
         };
         SC_TIME(1);  // chunk prologue: unpack, gate, softplus
-#if SC_BWD_UNROLL_NP
 #pragma unroll
-#endif
         for (int np = 0; np < NP; ++np, ++tix) {
             const int buf = (NPC && (NPC % 2) == 0) ? (np & 1) : (tix & 1);  // an even pair count: the parity restarts with every chunk
             const bool more = (np + 1 < NP) || (c > 0);
@@ -541,7 +508,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
             }
             const float* tB = smem + buf * 2 * TILE + lane * ROW;
             const float* tC = tB + TILE;
-            float* aB = acc + (SC_SLAB_BUFS == 2 ? buf : 0) * ACC_BUF + wave * 2 * ACC_TILE + lane * 2;  // (i, s) at aB[i * ACC_ISTR + s]: 8-byte stride
+            float* aB = acc + buf * ACC_BUF + wave * 2 * ACC_TILE + lane * 2;  // (i, s) at aB[i * ACC_ISTR + s]: 8-byte stride
             float* aC = aB + ACC_TILE;
             const int n0 = 2 * np;
             const f32x2 Av = readlane2(Areg, np);
@@ -630,10 +597,10 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                     if (i & 1) {
                         pkB = pB, pkC = pC;  // the odd item waits for its even partner: one 8-byte store per item pair
                     } else {
-                        // (8-byte stores at a 16-byte lane stride: 2-way bank conflicts, 31 % of the LDS cycles -- see
-                        // SC_BWD_SLAB_SWZ for the swizzle that removes them and why it is off)
-                        uint32_t* qB = accp + buf * PK_BUF + wave * 2 * PK_TILE + (i >> 2) * PK_Q + lane * 4 +
-                                       ((((i >> 1) ^ ((lane >> 3) & SC_BWD_SLAB_SWZ)) & 1) * 2);
+                        // (8-byte stores at a 16-byte lane stride: 2-way bank conflicts, 31 % of the LDS cycles.  Exchanging the item pairs
+                        // on lanes 8..15 of every 16 removes them and measured 1.5 % SLOWER: the 8 selects behind the MFMA cost more than
+                        // the conflicts, which hide -- profiles/r02_ablation_scan_bwd.txt, r05_ab_flush_placement.txt)
+                        uint32_t* qB = accp + buf * PK_BUF + wave * 2 * PK_TILE + (i >> 2) * PK_Q + lane * 4 + ((i >> 1) & 1) * 2;
                         if (!(SC_WHATIF & 32)) {
                             *(u32x2*)qB = u32x2{pB, pkB};
                             *(u32x2*)(qB + PK_TILE) = u32x2{pC, pkC};
@@ -679,8 +646,8 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 if (o2_row) sc_load_raw<T, SC_S, VEC>(o2_row, pn, L, rev, o2_raw);
             }
             // sum the SC_W regions and flush: thread t owns one tensor (dB / dC), one state of the pair and FT
-            // consecutive positions, stored 4 at a time (8/16-byte stores).  With two slab buffers the next pair writes
-            // the other buffer, so one barrier per pair suffices.
+            // consecutive positions, stored 4 at a time (8/16-byte stores).  The next pair writes the other slab buffer,
+            // so one barrier per pair suffices.
             if constexpr (CO) continue;  // no slab, no flush
             if constexpr (PACKED) {
                 if (!(SC_WHATIF & 32)) {
@@ -690,18 +657,13 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 const uint32_t* src = accp + buf * PK_BUF + ten * PK_TILE + (jb * 16 + jl) * 4 + g * (2 * PK_TILE);
                 f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int hf = 0; hf < SC_W / 4; ++hf) {  // (K = 32 = four channels x 8 elements per matrix product)
+                for (int hf = 0; hf < 2; ++hf) {  // (K = 32 = four channels x 8 elements per matrix product: two for the 8 channels)
                     const u32x4 b0 = *(const u32x4*)(src + hf * (8 * PK_TILE));
                     const u32x4 b1 = *(const u32x4*)(src + hf * (8 * PK_TILE) + PK_Q);
                     d0 = cad_mfma_16x16x32_bf16(selA, b0, d0);
                     d1 = cad_mfma_16x16x32_bf16(selA, b1, d1);
                 }
-                // lanes 0..31: g = state of the pair; d0 = items 0..3, d1 = items 4..7 of lane (jb, jl); pieces of lanes with
-                // bit 3 set were stored with their item pairs exchanged (bank swizzle of the slab writes)
-                if (SC_BWD_SLAB_SWZ && (jl & 8)) {
-                    d0 = f32x4{d0[2], d0[3], d0[0], d0[1]};
-                    d1 = f32x4{d1[2], d1[3], d1[0], d1[1]};
-                }
+                // lanes 0..31: g = state of the pair; d0 = items 0..3, d1 = items 4..7 of lane (jb, jl)
                 if (!(SC_WHATIF & 1) && g < 2 && n0 + g < N) {
                     const int64_t p = base + (int64_t)(jb * 16 + jl) * SC_S;
                     // row (state n0 + g) of this workgroup's slot: scalar base + one per-lane select (g is 0 or 1 here)
@@ -728,22 +690,17 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                     }
                 }
                 };  // flush_tile
-#if SC_BWD_FLUSH_HALF == 0
-                flush_tile(wave >> 2, wave & 3);  // every wave one tile pair (rounds 2-4)
-#else
-                // the STAGING waves 0-3 flush both tensors of their lane block, waves 4-7 go straight on (SC_BWD_FLUSH_HALF = 2: the other
-                // way round).  Waves 4-7 are the ones that reach the pair-step's barrier last (each shares its SIMD with a staging wave that
-                // wins the VALU arbitration by age, then waits for its tile loads): the flush -- LDS reads, four matrix products, a store,
-                // hardly any VALU work -- costs the staging waves waiting time they have and takes ~30 instructions + a latency chain out of
-                // the critical waves' pair-step.  Same-box: 3.391 vs 3.458 ms (-1.9 %); the other half: +1.2 % (profiles/r05_ab_flush_placement.txt).
+                // the STAGING waves 0-3 flush both tensors of their lane block, waves 4-7 go straight on.  Waves 4-7 are the ones that reach
+                // the pair-step's barrier last (each shares its SIMD with a staging wave that wins the VALU arbitration by age, then waits
+                // for its tile loads): the flush -- LDS reads, four matrix products, a store, hardly any VALU work -- costs the staging waves
+                // waiting time they have and takes ~30 instructions + a latency chain out of the critical waves' pair-step.  Same-box: 3.391
+                // vs 3.458 ms (-1.9 %) against one tile pair per wave; the other half: +1.2 % (profiles/r05_ab_flush_placement.txt).
                 // (NOT unrolled: with both tiles' address arithmetic hoisted out of the chunk loop the kernel spills -- 256 VGPRs + 156 bytes
                 // of scratch, +24 % -- while this form needs 223.)
-                // (SC_W = 4, two workgroups per CU: every wave stages and flushes -- its own lane block)
-                if (SC_W == 4 || (wave < SC_W / 2) == (SC_BWD_FLUSH_HALF == 1)) {  // wave-uniform
+                if (wave < SC_W / 2) {  // wave-uniform
 #pragma unroll 1
                     for (int ften = 0; ften < 2; ++ften) flush_tile(ften, wave & 3);
                 }
-#endif
                 }  // SC_WHATIF & 32
             } else {
                 constexpr int QT = 64 * SC_W / 4;     // threads per (tensor, state)
@@ -751,7 +708,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                 constexpr int FV = FT < 4 ? FT : 4;   // ... stored FV at a time
                 const int t = threadIdx.x;
                 const int ten = t / (2 * QT), s = (t / QT) & 1, idx = t % QT;
-                const float* tile = acc + (SC_SLAB_BUFS == 2 ? buf : 0) * ACC_BUF + ten * ACC_TILE;
+                const float* tile = acc + buf * ACC_BUF + ten * ACC_TILE;
                 TS* grow = (ten ? dCg : dBg) + ((int64_t)(n0 + s) * SB + sb) * L;
 #pragma unroll
                 for (int h4 = 0; h4 < FT; h4 += FV) {
@@ -787,7 +744,6 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_bwd_kernel(ScanBwdSets
                     }
                 }
             }
-            if (SC_SLAB_BUFS == 1) __syncthreads();  // the slab is rewritten by the next pair
             SC_TIME(11);  // next chunk's loads issued + flush
         }
         if constexpr (PREF && !CO) chunk_epilogue();
@@ -926,324 +882,6 @@ __global__ __launch_bounds__(64 * GF_WAVES) void scan_gate_fix_kernel(cad_scan_b
     }
 }
 
-// dst[i] = sum_k src[k * n + i]  (partial slots in T, fp32 accumulation); 4 elements per thread
-template <typename T>
-__device__ __forceinline__ void ld4p(const T* p, float* o);
-template <>
-__device__ __forceinline__ void ld4p<float>(const float* p, float* o) {
-    struct __attribute__((aligned(16))) V { float f[4]; };
-    const V t = *(const V*)p;
-    o[0] = t.f[0], o[1] = t.f[1], o[2] = t.f[2], o[3] = t.f[3];
-}
-template <>
-__device__ __forceinline__ void ld4p<bf16_t>(const bf16_t* p, float* o) {
-    struct __attribute__((aligned(8))) V { uint32_t w[2]; };
-    const V t = *(const V*)p;
-    o[0] = cad_bits2f(t.w[0] << 16), o[1] = cad_bits2f(t.w[0] & 0xffff0000u);
-    o[2] = cad_bits2f(t.w[1] << 16), o[3] = cad_bits2f(t.w[1] & 0xffff0000u);
-}
-
-// T = the destination's element type; the slots are in cad_slot_of<T> (bf16 for an fp16 destination)
-template <typename T>
-__global__ void reduce_partials_kernel(const typename cad_slot_of<T>::type* src, int nparts, int64_t n, T* dst, int vec) {
-    typedef typename cad_slot_of<T>::type TS;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-        // (the library's one summation order, include/caduceus_hip.h: groups of CAD_FOLD_GROUP consecutive slots, then the group sums)
-        if (vec && i + 4 <= n) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int k0 = 0; k0 < nparts; k0 += CAD_FOLD_GROUP) {
-                float g[4] = {0.f, 0.f, 0.f, 0.f};
-                for (int k = k0; k < nparts && k < k0 + CAD_FOLD_GROUP; ++k) {
-                    float x[4];
-                    ld4p<TS>(src + (int64_t)k * n + i, x);
-                    g[0] += x[0], g[1] += x[1], g[2] += x[2], g[3] += x[3];
-                }
-                s[0] += g[0], s[1] += g[1], s[2] += g[2], s[3] += g[3];
-            }
-            cad_cvt_store<T, 4>(dst + i, s);
-        } else {
-            for (int64_t q = i; q < n && q < i + 4; ++q) {
-                float acc = 0.f;
-                for (int k0 = 0; k0 < nparts; k0 += CAD_FOLD_GROUP) {
-                    float g = 0.f;
-                    for (int k = k0; k < nparts && k < k0 + CAD_FOLD_GROUP; ++k) g += to_f32(src[(int64_t)k * n + q]);
-                    acc += g;
-                }
-                dst[q] = from_f32<T>(acc);
-            }
-        }
-    }
-}
-
-// several folds of the same depth and length in one launch (blockIdx.y = job): the dB and dC slots of both parameter sets of a layer
-struct ReduceJobs {
-    const void* src[CAD_REDUCE_MAX_JOBS];
-    void* dst[CAD_REDUCE_MAX_JOBS];
-};
-template <typename T>
-__global__ void reduce_partials_multi_kernel(ReduceJobs jobs, int nparts, int64_t n) {
-    typedef typename cad_slot_of<T>::type TS;
-    const TS* src = (const TS*)jobs.src[blockIdx.y];
-    T* dst = (T*)jobs.dst[blockIdx.y];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {  // (n % 4 == 0, 16-byte aligned: checked)
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < nparts; k0 += CAD_FOLD_GROUP) {
-            float g[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int k = k0; k < nparts && k < k0 + CAD_FOLD_GROUP; ++k) {
-                float x[4];
-                ld4p<TS>(src + (int64_t)k * n + i, x);
-                g[0] += x[0], g[1] += x[1], g[2] += x[2], g[3] += x[3];
-            }
-            s[0] += g[0], s[1] += g[1], s[2] += g[2], s[3] += g[3];
-        }
-        cad_cvt_store<T, 4>(dst + i, s);
-    }
-}
-
-// ---- the dB / dC fold behind a RUNNING scan backward (cad_fold_partials_stream, include/caduceus_hip.h) -----------------------------
-// One workgroup per (slice x of a chunk, row, parameter set), 256 threads.  A 512-position chunk of a row's dB / dC is 2 N rows x 512
-// bf16; slice x is elements [x EPW, (x + 1) EPW) of it, EPW = 2 N 512 / n_partials (256 at configs[2]: half a row).  Per slot the
-// slice is VPS = EPW / 8 16-byte vectors; thread t owns vector t % VPS of the CAD_FOLD_GROUP = 8 slots of group t / VPS (8 loads in
-// flight per thread, 32 KB per workgroup), sums them in slot order, and the first VPS threads add the group sums in group order
-// through LDS: the library's one summation order, bit-identical to cad_reduce_partials_multi.  Chunks are taken in the order the scan
-// produces them (last logical chunk first); a right-to-left row's logical chunk c lies at physical positions L - (c + 1) 512.
-#define FOLD_T 256
-#define FOLD_CHUNK 512
-struct FoldSets {
-    cad_fold_args s[SC_MAXSETS];
-};
-// Placement gate.  The fold kernel must reach a CU AFTER the scan workgroup it shares that CU with: a 48-VGPR / 10 KB allocation that
-// lands first -- or next to the waves of a third kernel that then leave (the carry pass of an L-split backward, an RCCL all-reduce) --
-// sits in the MIDDLE of the register file / LDS and leaves no contiguous 2 x 232 VGPRs / 132 KB for the scan workgroup: measured, the
-// full pass of an L-split backward did not start until the fold gave up 20 ms later (profiles/r06_ab_stream_fold.txt).  So one wave runs
-// AHEAD of the fold kernel on its stream and returns only when the scan's workgroups have been placed: every scan workgroup adds 1 to
-// counters[SB x nchunks] as it starts; the gate waits for the first arrival, then until the count has stopped rising for ~20 us (a whole
-// grid is dispatched within a microsecond; a launch with more workgroups than CUs stalls at the resident ones) or the budget is spent.
-__global__ __launch_bounds__(64) void fold_gate_kernel(FoldSets sets, int nsets, int want, uint64_t budget_ticks) {
-    if (threadIdx.x != 0) return;
-    const uint64_t t0 = cad_wall_clock();
-    int last = -1;
-    uint64_t t_change = t0;
-    for (;;) {
-        int n = 0;
-        for (int i = 0; i < nsets; ++i) {
-            const cad_fold_args& a = sets.s[i];
-            n += cad_counter_load_agent(a.counters + a.SB * (a.L / FOLD_CHUNK));
-        }
-        const uint64_t now = cad_wall_clock();
-        if (n >= want) return;
-        if (n != last) last = n, t_change = now;
-        if (n > 0 && now - t_change >= 2000) return;   // 20 us without a new workgroup: everything that fits is resident
-        if (now - t0 >= budget_ticks) return;          // the scan is not running next to us: the fold kernel deals with that itself
-        cad_poll_sleep();
-    }
-}
-
-#define FOLD_MAX_ITEMS 256  // items (slice, row, set) one workgroup may be given
-#ifndef FOLD_WAKE_DIV
-#define FOLD_WAKE_DIV 4
-#endif
-__global__ __launch_bounds__(FOLD_T) void fold_stream_kernel(FoldSets sets, int nsets, int mode, uint64_t budget_ticks) {
-    // One launch has AT MOST one workgroup per CU (the host passes the CU count as the grid limit): a second resident fold workgroup would
-    // take the registers the next scan workgroup needs on that CU (2 x 232 + 2 x 48 > 512 VGPRs per SIMD) and starve the scan of launches
-    // with more workgroups than CUs (configs[4]: measured +19 % per layer with one fold workgroup per item).  Items beyond the grid are
-    // taken by the same workgroups, item = blockIdx.x + j gridDim.x -- in the order the scan's workgroups are dispatched, and never
-    // blocking on one item while another has a chunk ready.
-    __shared__ float part[FOLD_T / 2 * 8];
-    __shared__ int nextc[FOLD_MAX_ITEMS];  // next chunk of item j (chunks are taken from the last logical one down); < 0: done
-    __shared__ int pick_s[2];              // {item to fold now or -1, give up}
-    const int t = threadIdx.x;
-    const cad_fold_args& a0 = sets.s[0];
-    const int G = a0.n_partials, N = a0.N;
-    const int64_t L = a0.L, SB = a0.SB;
-    const int64_t nchunks = L / FOLD_CHUNK;
-    const int total = G * (int)SB * nsets;
-    const int nitems = (total - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int EPW = 2 * N * FOLD_CHUNK / G, VPS = EPW / 8, NG = G / CAD_FOLD_GROUP;  // NG x VPS = 16 N threads work (all 256 at d_state 16)
-    const bool active = t < NG * VPS;
-    const int v = t % VPS, grp = active ? t / VPS : 0;
-    const int64_t part_stride = (int64_t)N * SB * L;
-    auto item_set = [&](int j) { return (blockIdx.x + j * gridDim.x) / (G * (int)SB); };
-    auto item_row = [&](int j) { return ((blockIdx.x + j * gridDim.x) / G) % (int)SB; };
-    auto item_slice = [&](int j) { return (blockIdx.x + j * gridDim.x) % G; };
-    auto abort_slot = [&](int j) -> int* {
-        const cad_fold_args& a = sets.s[item_set(j)];
-        return a.abort_from ? a.abort_from + (int64_t)item_row(j) * G + item_slice(j) : nullptr;
-    };
-    if (mode == CAD_FOLD_CONCURRENT) {
-        // co-location check (see scan_bwd_kernel): not next to a scan workgroup AND scan workgroups still unplaced -> this workgroup is
-        // in their way (its registers / LDS sit where theirs must go): hand everything to the cleanup launch and leave
-        if (t == 0) {
-            int started = 0, here = 0;
-            const int key = cad_cu_key();
-            for (int i = 0; i < nsets; ++i) {
-                const int* base = sets.s[i].counters + sets.s[i].SB * nchunks;
-                started += cad_counter_load_agent(base);
-                here += cad_counter_load_agent(base + 1 + key);
-            }
-            pick_s[0] = (here == 0 && started < total) ? 1 : 0;
-        }
-        __syncthreads();
-        if (pick_s[0]) {
-            for (int j = t; j < nitems; j += FOLD_T) {
-                int* as = abort_slot(j);
-                if (as) *as = (int)nchunks;
-            }
-            return;
-        }
-        __syncthreads();  // pick_s is rewritten below
-    }
-    for (int j = t; j < nitems; j += FOLD_T) {
-        int c = (int)nchunks - 1;
-        if (mode == CAD_FOLD_CLEANUP) {  // what a concurrent pass left (stored as chunk + 1: 0 = nothing)
-            int* as = abort_slot(j);
-            c = (as ? *as : 0) - 1;
-            if (as) *as = 0;
-        }
-        nextc[j] = c;
-    }
-    __syncthreads();
-    int first = 0;  // (thread 0 only) items before `first` are done
-    uint64_t t_last = (mode == CAD_FOLD_CONCURRENT && t == 0) ? cad_wall_clock() : 0;
-    // Polling costs the scan next door (every poll is a load through the CU's memory pipeline that its staging waves wait on: same-box
-    // A/B, layer 7.60 -> 7.49 ms with 4x longer sleeps): thread 0 learns the cadence of the arrivals (a chunk every ~13 us) and sleeps
-    // through most of the predicted gap after a fold -- one or two failed polls per chunk instead of five to ten.
-    uint64_t period = 0;       // ticks between the last two picks that had to wait (0: unknown)
-    uint64_t t_wake = 0;       // do not poll before this time
-    for (;;) {
-        // ---- choose: the first item (in dispatch order) whose next chunk is complete; at most 4 pending items are polled per round
-        if (t == 0) {
-            int pick = -1, give_up = 0, alive = 0;
-            while (first < nitems && nextc[first] < 0) ++first;
-            bool waited = false;
-            for (;;) {
-                if (mode == CAD_FOLD_CONCURRENT && t_wake) {
-                    while (cad_wall_clock() < t_wake) cad_poll_sleep();
-                    t_wake = 0;
-                }
-                int polled = 0;
-                alive = 0;
-                for (int j = first; j < nitems && pick < 0 && polled < 4; ++j) {
-                    const int c = nextc[j];
-                    if (c < 0) continue;
-                    alive = 1;
-                    if (mode != CAD_FOLD_CONCURRENT) {
-                        pick = j;
-                    } else {
-                        const cad_fold_args& a = sets.s[item_set(j)];
-                        ++polled;
-                        if (cad_counter_load_agent(a.counters + (int64_t)item_row(j) * nchunks + c) >= G) pick = j;
-                    }
-                }
-                if (pick >= 0 || !alive) break;
-                if (cad_wall_clock() - t_last >= budget_ticks) {  // no arrival anywhere for the whole budget: not co-scheduled with a
-                    give_up = 1;                                  // progressing scan -- leave the rest to the cleanup launch
-                    break;
-                }
-                waited = true;
-                cad_poll_sleep();
-            }
-            if (pick >= 0 && mode == CAD_FOLD_CONCURRENT) {
-                const uint64_t now = cad_wall_clock();
-                if (waited) {  // steady state: this chunk arrived while we were watching -- the next one is a period away
-                    if (t_last) period = now - t_last;
-                    if (period > 5000) period = 5000;           // (50 us: never sleep long on a stale estimate)
-                    t_wake = now + period - period / FOLD_WAKE_DIV;  // wake a fraction of the period early
-                }
-                t_last = now;
-            }
-            pick_s[0] = pick, pick_s[1] = give_up;
-        }
-        __syncthreads();
-        const int j = cad_uniform(pick_s[0]);  // (workgroup-uniform: everything derived from the item stays in scalar registers)
-        if (j < 0) {
-            if (pick_s[1]) {
-                for (int q = t; q < nitems; q += FOLD_T) {
-                    int* as = abort_slot(q);
-                    if (nextc[q] >= 0 && as) *as = nextc[q] + 1;
-                }
-            }
-            return;  // everything folded, or given up
-        }
-        const int64_t c = cad_uniform(nextc[j]);
-        // ---- fold chunk c of item j
-        const cad_fold_args& a = sets.s[item_set(j)];
-        const int x = item_slice(j);
-        const int64_t sb = item_row(j);
-        const int e0 = x * EPW + v * 8, r = e0 / FOLD_CHUNK, p = e0 % FOLD_CHUNK;
-        const int ten = cad_uniform((x * EPW) / (N * FOLD_CHUNK));  // a slice (EPW divides N 512) never straddles the two tensors: per WORKGROUP
-        const int n = r % N;
-        const int rev = sb < a.split ? a.rev_lo : a.rev_hi;
-        const int64_t cphys = rev ? L - (c + 1) * FOLD_CHUNK : c * FOLD_CHUNK;
-        // element offsets inside one tensor's slots fit 32 bits (the launcher checks n_partials N SB L 2 < 2^32): lane arithmetic in 32 bits
-        const uint32_t row_off = ((uint32_t)n * (uint32_t)SB + (uint32_t)sb) * (uint32_t)L + (uint32_t)p + (uint32_t)cphys;
-        // slot k of the lane's group at (workgroup-uniform base of the tensor + k part_stride, scalar registers) + a 32-bit lane offset
-        const char* tbase = (const char*)(ten ? a.dC_slots : a.dB_slots);
-        const uint32_t voff = ((uint32_t)(grp * CAD_FOLD_GROUP) * (uint32_t)part_stride + row_off) * 2u;
-        char* dbase = (char*)(ten ? a.dC : a.dB);
-        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (active) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {  // two rounds of four loads: 16 data registers instead of 32
-                const void* base[4];
-                u32x4 w[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) base[k] = tbase + (int64_t)(4 * h + k) * part_stride * 2;
-                cad_load16x4_wt(base, voff, w);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        s[2 * q] += cad_bits2f(w[k][q] << 16);
-                        s[2 * q + 1] += cad_bits2f(w[k][q] & 0xffff0000u);
-                    }
-                }
-                // the sums of this round exist before the next round's loads are issued (otherwise the scheduler hoists those loads
-                // and both rounds' 32 data registers are live at once: 52 instead of 40 VGPRs)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) cad_order_point(s[q]);
-            }
-        }
-        // group sums through LDS in two rounds (groups 1 .. NG/2 - 1, then NG/2 .. NG - 1): half the staging area -- 4 KB, so that the
-        // workgroup fits behind TWO resident 76 KB scan workgroups (SC_W_BWD = 4) as well as behind one of 132 KB -- same order of additions
-        const int gh = NG / 2;
-        if (active && grp > 0 && grp < gh) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) part[(grp * VPS + v) * 8 + q] = s[q];
-        }
-        __syncthreads();
-        if (active && grp == 0) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s[q] = 0.f + s[q];  // (group 0 first: the accumulator of the group sums starts from 0)
-#pragma unroll 1
-            for (int g = 1; g < gh; ++g) {  // (not unrolled: the kernel must fit the 48 VGPRs two resident scan waves leave on a SIMD)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s[q] += part[(g * VPS + v) * 8 + q];
-            }
-        }
-        __syncthreads();
-        if (active && grp > 0 && grp >= gh) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) part[((grp - gh) * VPS + v) * 8 + q] = s[q];
-        }
-        __syncthreads();
-        if (active && grp == 0) {
-#pragma unroll 1
-            for (int g = (gh > 1 ? gh : 1); g < NG; ++g) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s[q] += part[((g - gh) * VPS + v) * 8 + q];
-            }
-            u32x4 ov;
-            ov[0] = cad_pack_bf16x2(s[0], s[1]), ov[1] = cad_pack_bf16x2(s[2], s[3]);
-            ov[2] = cad_pack_bf16x2(s[4], s[5]), ov[3] = cad_pack_bf16x2(s[6], s[7]);
-            *(u32x4*)(dbase + row_off * 2u) = ov;
-        }
-        if (t == 0) nextc[j] = (int)c - 1;
-        __syncthreads();  // `part`, nextc and pick_s are rewritten by the next round
-    }
-}
 
 }  // namespace
 
@@ -1291,24 +929,20 @@ extern "C" int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void
     for (int i = 0; i < nsets; ++i) CAD_CHECK_ARG(sets[i].carry_only || !sets[i].fold_counters || vec);  // (16-byte write-through slot stores)
     CadProfScope prof(1, stream);
     dim3 grid((unsigned)((a->E + SC_W - 1) / SC_W), (unsigned)a->SB, (unsigned)nsets), block(64 * SC_W);
-    const bool packed = SC_SLAB_PACKED && a->dtype == CAD_BF16 && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;
-    const bool pref = SC_BWD_PREFETCH && packed && vec && SC_S * 2 == 16;
+    const bool packed = a->dtype == CAD_BF16;  // the kernel's PACKED / PREF
+    const bool pref = packed && vec;
     bool all_dt = true;  // every set hands over dt itself: the lean production instantiation (ISDT)
     for (int i = 0; i < nsets; ++i) all_dt = all_dt && sets[i].delta_is_dt != 0;
-    const size_t slab_floats = a->carry_only ? 0 : (packed ? 2 * PK_BUF : SC_SLAB_BUFS * ACC_BUF);
+    const size_t slab_floats = a->carry_only ? 0 : (packed ? 2 * PK_BUF : 2 * ACC_BUF);
     const size_t shmem = (size_t)(4 * SC_TILE(SC_S) + slab_floats) * sizeof(float) +
                          (pref ? PRE_BYTES : 0);
-    // The lean production instantiation (ISDT) exists only in builds whose tuning defines allow it (its static_assert: LDS-DMA prefetch,
-    // packed slab, 8-wave workgroups, unrolled pair loop): in every other variant build (-DSC_BWD_PREFETCH=0, -DSC_SLAB_PACKED=0, -DSC_W_BWD=4,
-    // -DSC_BWD_UNROLL_NP=0, -DSC_BWD_LEAN=0) the template argument below is `false` and the branch is the unrolled round-4 kernel again.
-    constexpr bool kLeanBuild = SC_BWD_LEAN && (SC_BWD_UNROLL_NP != 0) && SC_BWD_PREFETCH && SC_SLAB_PACKED && (SC_W == 8 || SC_W == 4) && SC_SLAB_BUFS == 2;
+    // (V && bf16 is `pref`, a compile-time fact of the branch: the lean instantiation's static_assert holds for no other T / V)
 #define SC_BWD_LAUNCH(T, V)                                                                  \
     do {                                                                                     \
-        if (kLeanBuild && SC_BWD_UNROLL_NP && !a->carry_only && V && cad_is_bf16<T>::value && pref && all_dt &&   \
-            a->N == 2 * SC_BWD_UNROLL_NP) {                                                  \
-            SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && cad_is_bf16<T>::value>), shmem);             \
-            CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, kLeanBuild && V && cad_is_bf16<T>::value>), grid, block, shmem, stream, ks); \
-        } else if (SC_BWD_UNROLL_NP && !a->carry_only && V && sizeof(T) == 2 && a->N == 2 * SC_BWD_UNROLL_NP) { \
+        if (!a->carry_only && V && cad_is_bf16<T>::value && all_dt && a->N == 2 * SC_BWD_UNROLL_NP) { \
+            SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, V && cad_is_bf16<T>::value>), shmem); \
+            CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP, V && cad_is_bf16<T>::value>), grid, block, shmem, stream, ks); \
+        } else if (!a->carry_only && V && sizeof(T) == 2 && a->N == 2 * SC_BWD_UNROLL_NP) {  \
             SC_BIG_LDS((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP>), shmem);             \
             CAD_LAUNCH((scan_bwd_kernel<T, V, false, SC_BWD_UNROLL_NP>), grid, block, shmem, stream, ks); \
         } else if (a->carry_only) {                                                          \
@@ -1343,14 +977,6 @@ extern "C" int cad_scan_bwd_multi(const cad_scan_bwd_args* sets, int nsets, void
 
 extern "C" int cad_scan_bwd(const cad_scan_bwd_args* a, void* stream) { return cad_scan_bwd_multi(a, 1, stream); }
 
-// diagnostic (tools/gpu_w4.sh): how many workgroups of the production instantiation the runtime places on one CU, and its LDS bytes
-extern "C" int cad_debug_scan_bwd_occupancy(int* out) {
-    const size_t shmem = (size_t)(4 * SC_TILE(SC_S) + 2 * PK_BUF) * sizeof(float) + PRE_BYTES;
-    out[0] = CAD_OCCUPANCY((scan_bwd_kernel<bf16_t, true, false, SC_BWD_UNROLL_NP>), 64 * SC_W, shmem);
-    out[1] = (int)shmem, out[2] = SC_W;
-    return out[0] > 0 ? CAD_OK : CAD_ERR_UNSUPPORTED;
-}
-
 extern "C" int64_t cad_scan_gate_fix_entries(int E, int64_t SB, int64_t L) {
     return (int64_t)E * SB * ((L + SC_CHUNK - 1) / SC_CHUNK);
 }
@@ -1380,126 +1006,7 @@ extern "C" int cad_scan_bwd_gate_fix(const cad_scan_bwd_args* sets, int nsets, v
     return cad_after_launch();
 }
 
-namespace {
-__global__ __launch_bounds__(64) void stream_probe_wait_kernel(const int* flag, int* result, uint64_t budget_ticks) {
-    if (threadIdx.x != 0) return;
-    const uint64_t t0 = cad_wall_clock();
-    int seen = 0;
-    do {
-        seen = cad_counter_load_agent(flag) != 0;
-        if (!seen) cad_poll_sleep();
-    } while (!seen && cad_wall_clock() - t0 < budget_ticks);
-    result[0] = seen;
-}
-__global__ __launch_bounds__(64) void stream_probe_set_kernel(int* flag) {
-    if (threadIdx.x == 0) cad_counter_add_agent(flag, 1);
-}
-}  // namespace
-
-extern "C" int cad_stream_probe(void* stream_a, void* stream_b, int* flag, int* result, int64_t budget_us) {
-    CAD_CHECK_ARG(flag && result && budget_us > 0 && budget_us <= 1000000);
-    CAD_LAUNCH(stream_probe_wait_kernel, dim3(1), dim3(64), 0, stream_a, (const int*)flag, result,
-               (uint64_t)budget_us * CAD_WALL_CLOCK_TICKS_PER_US);
-    CAD_LAUNCH(stream_probe_set_kernel, dim3(1), dim3(64), 0, stream_b, flag);
-    return cad_after_launch();
-}
-
 extern "C" int64_t cad_scan_bwd_chunk_len(void) { return SC_CHUNK; }
 extern "C" int64_t cad_scan_bwd_fold_counter_ints(int64_t SB, int64_t L) {
     return SB * ((L + SC_CHUNK - 1) / SC_CHUNK) + 1 + CAD_CU_KEYS;
-}
-
-extern "C" int cad_fold_stream_supported(int N, int n_partials, int64_t L, int dtype) {
-    if (dtype != CAD_BF16 || N < 1 || L < FOLD_CHUNK || L % FOLD_CHUNK != 0 || SC_CHUNK != FOLD_CHUNK) return 0;
-    if (n_partials < CAD_FOLD_GROUP || n_partials > 2048 || (n_partials & (n_partials - 1)) != 0) return 0;
-    const int elems = 2 * N * FOLD_CHUNK;
-    if (elems % n_partials != 0) return 0;
-    const int epw = elems / n_partials;
-    if (epw < 8 || epw % 8 != 0) return 0;
-    if (n_partials % CAD_FOLD_GROUP != 0) return 0;  // whole groups of 8 slots
-    const int vps = epw / 8;                         // vectors per slot and workgroup; (n_partials / 8) x vps = 16 N threads work
-    if ((n_partials / CAD_FOLD_GROUP) * vps > FOLD_T) return 0;    // d_state <= 16
-    if (FOLD_CHUNK % epw != 0 && epw % FOLD_CHUNK != 0) return 0;  // a slice lies inside one row, or covers whole rows
-    if ((N * FOLD_CHUNK) % epw != 0) return 0;                     // ... and inside one tensor
-    // (8-wave workgroups only: the 4-wave variant -- two workgroups per CU, profiles/r06_ab_w4_workgroups.txt -- fails one device test next to
-    // the concurrent fold and is 15 % slower without it)
-    return SC_BWD_SLOT_WT && SC_SLAB_PACKED && SC_W == 8 && SC_SLAB_BUFS == 2;  // the write-through slot stores of the packed flush
-}
-
-extern "C" int cad_fold_partials_stream(const cad_fold_args* sets, int nsets, int mode, void* stream) {
-    CAD_CHECK_ARG(sets && nsets >= 1 && nsets <= SC_MAXSETS);
-    CAD_CHECK_ARG(mode == CAD_FOLD_CONCURRENT || mode == CAD_FOLD_CLEANUP || mode == CAD_FOLD_ALL);
-    FoldSets ks;
-    for (int i = 0; i < nsets; ++i) {
-        const cad_fold_args* a = &sets[i];
-        CAD_CHECK_ARG(a->dB_slots && a->dC_slots && a->dB && a->dC && a->SB > 0 && a->SB <= 65535);
-        CAD_CHECK_ARG(a->split >= 0 && a->split <= a->SB);
-        if (!cad_fold_stream_supported(a->N, a->n_partials, a->L, a->dtype)) return CAD_ERR_UNSUPPORTED;
-        CAD_CHECK_ARG((((uintptr_t)a->dB_slots | (uintptr_t)a->dC_slots | (uintptr_t)a->dB | (uintptr_t)a->dC) % 16) == 0);
-        if ((int64_t)a->n_partials * a->N * a->SB * a->L * 2 >= ((int64_t)1 << 32)) return CAD_ERR_UNSUPPORTED;  // 32-bit lane offsets (per tensor)
-        CAD_CHECK_ARG(mode != CAD_FOLD_CONCURRENT || (a->counters && a->abort_from));
-        CAD_CHECK_ARG(mode != CAD_FOLD_CLEANUP || a->abort_from);
-        CAD_CHECK_ARG(a->N == sets[0].N && a->n_partials == sets[0].n_partials && a->L == sets[0].L && a->SB == sets[0].SB);
-        ks.s[i] = *a;
-    }
-    for (int i = nsets; i < SC_MAXSETS; ++i) ks.s[i] = sets[0];
-    // a poll that sees no arrival for this long gives the chunk (and the rest of the row slice) to the cleanup launch: the scan produces a
-    // chunk every ~13 us, so 20 ms means "the scan is not running next to us" (serialised queues, a profiler, a debugger)
-    const uint64_t budget = 2000000ull;  // ticks of the 100 MHz wall clock
-    const int64_t items = (int64_t)sets[0].n_partials * sets[0].SB * nsets;
-    const int cus = cad_cu_count();  // one workgroup per CU at most (see the kernel)
-    if (items > (int64_t)cus * FOLD_MAX_ITEMS) return CAD_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)(items < cus ? items : cus)), block(FOLD_T);
-    if (mode == CAD_FOLD_CONCURRENT)  // (same stream: the fold kernel is dispatched when the gate has returned)
-        CAD_LAUNCH(fold_gate_kernel, dim3(1), dim3(64), 0, stream, ks, nsets, (int)items, budget);
-    CAD_LAUNCH(fold_stream_kernel, grid, block, 0, stream, ks, nsets, mode, budget);
-    return cad_after_launch();
-}
-
-extern "C" int cad_reduce_partials(const void* src, int n_partials, int64_t n, void* dst, int dst_dtype, void* stream) {
-    CAD_CHECK_ARG(src && dst && n_partials >= 1 && n > 0);
-    const int vec = (n % 4) == 0 && (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
-    int64_t nb = (n / 4 + 255) / 256 + 1;
-    if (nb > 16384) nb = 16384;
-    dim3 grid((unsigned)nb), block(256);
-    if (dst_dtype == CAD_F32)
-        CAD_LAUNCH((reduce_partials_kernel<float>), grid, block, 0, stream, (const float*)src, n_partials, n, (float*)dst, vec);
-    else if (dst_dtype == CAD_BF16)
-        CAD_LAUNCH((reduce_partials_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)src, n_partials, n, (bf16_t*)dst, vec);
-    else if (dst_dtype == CAD_F16)  // bf16 slots (the scan backward's fp16 mode)
-        CAD_LAUNCH((reduce_partials_kernel<f16_t>), grid, block, 0, stream, (const bf16_t*)src, n_partials, n, (f16_t*)dst, vec);
-    else
-        return CAD_ERR_UNSUPPORTED;
-    return cad_after_launch();
-}
-
-extern "C" int cad_reduce_partials_multi(const cad_reduce_job* jobs, int njobs, int n_partials, int64_t n, int dst_dtype, void* stream) {
-    CAD_CHECK_ARG(jobs && njobs >= 1 && njobs <= CAD_REDUCE_MAX_JOBS && n_partials >= 1 && n > 0);
-    ReduceJobs kj;
-    bool vec = (n % 4) == 0;
-    for (int i = 0; i < CAD_REDUCE_MAX_JOBS; ++i) {
-        const cad_reduce_job& j = jobs[i < njobs ? i : 0];
-        CAD_CHECK_ARG(j.src && j.dst);
-        kj.src[i] = j.src, kj.dst[i] = j.dst;
-        vec = vec && (((uintptr_t)j.src | (uintptr_t)j.dst) % 16) == 0;
-    }
-    if (!vec) {  // ragged / unaligned: one plain fold per job
-        for (int i = 0; i < njobs; ++i) {
-            const int rc = cad_reduce_partials(jobs[i].src, n_partials, n, jobs[i].dst, dst_dtype, stream);
-            if (rc != CAD_OK) return rc;
-        }
-        return CAD_OK;
-    }
-    int64_t nb = (n / 4 + 255) / 256 + 1;
-    if (nb > 16384) nb = 16384;
-    dim3 grid((unsigned)nb, (unsigned)njobs), block(256);
-    if (dst_dtype == CAD_F32)
-        CAD_LAUNCH((reduce_partials_multi_kernel<float>), grid, block, 0, stream, kj, n_partials, n);
-    else if (dst_dtype == CAD_BF16)
-        CAD_LAUNCH((reduce_partials_multi_kernel<bf16_t>), grid, block, 0, stream, kj, n_partials, n);
-    else if (dst_dtype == CAD_F16)
-        CAD_LAUNCH((reduce_partials_multi_kernel<f16_t>), grid, block, 0, stream, kj, n_partials, n);
-    else
-        return CAD_ERR_UNSUPPORTED;
-    return cad_after_launch();
 }

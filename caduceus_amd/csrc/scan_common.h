@@ -16,25 +16,15 @@
 #pragma once
 #include "cad_common.h"
 
-// Tuning constants (overridable with -D for A/B builds).  The forward walks 1024-position chunks (16 items per lane);
-// the backward keeps ~2x more per-item state in registers and walks 512-position chunks (8 items per lane).  Both
-// index the saved running states by 512-position "half chunks" (SC_STATE_STEP).
-#ifndef SC_S_FWD
+// Tuning constants (the values measured best; the closed alternatives live in profiles/ and in git).  The forward walks
+// 1024-position chunks (16 items per lane); the backward keeps ~2x more per-item state in registers and walks 512-position
+// chunks (8 items per lane).  Both index the saved running states by 512-position "half chunks" (SC_STATE_STEP).
 #define SC_S_FWD 16
-#endif
-#ifndef SC_S_BWD
 #define SC_S_BWD 8
-#endif
-#ifndef SC_W_FWD
 #define SC_W_FWD 8              // waves (= channels) per forward workgroup (measured: 8 beats 4 by 13 %)
-#endif
-#ifndef SC_W_BWD
 #define SC_W_BWD 8              // waves (= channels) per backward workgroup: dB/dC are summed over them in LDS (4 = two workgroups per CU:
                                 // measured 15 % slower, profiles/r06_ab_w4_workgroups.txt)
-#endif
-#ifndef SC_OCC
 #define SC_OCC 2                // register budget: waves per SIMD the kernels are compiled for
-#endif
 #define SC_STATE_STEP (64 * SC_S_BWD)   // positions between saved running states = the backward's chunk
 // timing experiments only (WRONG results): what does a mechanism cost?  (tools/ab_train_scan.sh over -DSC_WHATIF=... builds)
 // SC_WHATIF_ARITH_ONLY = the backward's "stripped timing build" (VERDICT r3 item 1): no global stores, no dB/dC slab / flush, no B/C
@@ -356,23 +346,8 @@ static_assert(SC_NDMA == 6, "the immediate of s_waitcnt vmcnt(6) above");
 // Completion is tracked by vmcnt like any load (the issuing wave waits vmcnt(0) before its ds_read).
 __device__ __forceinline__ uint32_t sc_lds_off(const void* p) { return cad_lds_off(p); }
 __device__ __forceinline__ void sc_glds16(const void* gsrc, uint32_t lds_base) { cad_glds16(gsrc, lds_base); }
-// Static priority for the second half of a workgroup's waves (MI355X: of the two waves a 512-thread workgroup places on
-// each SIMD, the later-dispatched one loses VALU arbitration; measured here: waves 4-7 spend 1.2-2.3x the cycles of
-// waves 0-3 in the DPP / packed-FMA phases, profiles/r02_phase_timing_dma_prefetch.txt, while waves 0-3 -- which also do
-// the tile staging -- idle at the barrier).
-#ifndef SC_PRIO
-#define SC_PRIO 0   // (3 = every scan wave above the co-resident fold kernel's priority 0: -2.3 % per layer while that kernel polled every
-                    // ~0.5 us, nothing once it sleeps through the predicted gap between arrivals -- profiles/r06_ab_stream_fold.txt)
-#endif
-__device__ __forceinline__ void sc_static_priority(int wave, int nwaves) {
-#if SC_PRIO == 1 && !defined(CAD_EMU)
-    if (wave >= nwaves / 2) __builtin_amdgcn_s_setprio(1);  // wave is wave-uniform (readfirstlane): a scalar branch
-#elif SC_PRIO == 2 && !defined(CAD_EMU)
-    if (wave < nwaves / 2) __builtin_amdgcn_s_setprio(1);   // A/B: the staging half instead
-#elif SC_PRIO == 3 && !defined(CAD_EMU)
-    __builtin_amdgcn_s_setprio(1);  // every scan wave above the (priority 0) waves of a kernel that shares the CU: the concurrent dB / dC fold
-#endif
-}
+// (A static wave priority -- s_setprio for the later-dispatched half of a workgroup, or for every scan wave above the co-resident fold
+// kernel -- was tried and closed: nothing once the fold sleeps through the gap between arrivals, profiles/r06_ab_stream_fold.txt.)
 
 // Per-thread constants of the staging path, computed once per kernel: the thread's tensor base (+ its row sb) and its
 // first token inside a chunk.  Keeps the per-pair address arithmetic to one uniform multiply and two adds.

@@ -2,10 +2,6 @@
 // See scan_common.h for the decomposition.
 #include "scan_common.h"
 
-#ifndef SC_PRE_WAIT
-#define SC_PRE_WAIT 0   // 1: counted wait at the chunk start (leaves the most recent stores in flight)
-#endif
-
 namespace {
 
 struct ScanFwdSets {
@@ -17,29 +13,19 @@ struct ScanFwdSets {
 #define SC_CHUNK (64 * SC_S)
 // B/C tiles live in a ring of SC_RING_FWD LDS slots; a tile is staged SC_RING_FWD / 2 pairs ahead of its use and the
 // workgroup meets at a barrier once per SC_RING_FWD / 2 pairs (2: double buffer, one barrier per pair).
-#ifndef SC_OCC_FWD
-#define SC_OCC_FWD SC_OCC
-#endif
-// LDS-DMA prefetch of the next chunk's u / delta / z vectors (bf16 production kernel; see sc_glds16): 32-byte vectors =
+#define SC_RING_FWD 4                      // the prefetch slots take 64 KB of the LDS a ring of 8 used (-1.7 %)
+// LDS-DMA prefetch of the next chunk's u / delta / z vectors (16-bit vector kernels; see sc_glds16): 32-byte vectors =
 // two 16-byte planes per tensor; z is read at the END of a chunk, so it alternates between two slot pairs.
-#ifndef SC_FWD_DMA
-#define SC_FWD_DMA 1
-#endif
-#ifndef SC_RING_FWD
-#define SC_RING_FWD (SC_FWD_DMA ? 4 : 8)   // the prefetch slots take 64 KB of the LDS the deeper ring used (-1.7 %)
-#endif
 #define PRE_SLOT (SC_W * 64 * 16)          // bytes per 16-byte plane (all waves)
 #define PRE_BYTES (8 * PRE_SLOT)           // u0 u1 d0 d1 | z0 z1 (even chunks) | z0 z1 (odd chunks)
 
-// SC_FWD_UNROLL_NP = 8: the production instantiation (bf16, vector path, d_state = 16) has its pair loop fully unrolled, as the backward
-// (compile-time pair index: ring slot, barrier parity and staging cursor fold).  -DSC_FWD_UNROLL_NP=0: the run-time loop everywhere.
-#ifndef SC_FWD_UNROLL_NP
+// The production instantiation (bf16, vector path, d_state = 16 = SC_FWD_UNROLL_NP pairs) has its pair loop fully unrolled, as the
+// backward (compile-time pair index: ring slot, barrier parity and staging cursor fold).
 #define SC_FWD_UNROLL_NP 8
-#endif
 // MO = map-only instantiation (cad_scan_args.map_only, pass 1 of an L-split scan): recurrence and wave scan only -- hT and
 // sum_dt are the outputs; no C tile reads, no output phase, no gate, no stores of `out` / chunk states.
 template <typename T, bool VEC, bool MO, int NPC = 0>
-__global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwdSets sets) {
+__global__ __launch_bounds__(64 * SC_W, SC_OCC) void scan_fwd_kernel(ScanFwdSets sets) {
     CAD_DYN_SMEM(float, smem);  // [SC_RING_FWD slots][B,C][SC_TILE]
     constexpr int TILE = SC_TILE(SC_S), ROW = SC_ROW(SC_S);
     constexpr int RING = SC_RING_FWD, AHEAD = RING / 2;
@@ -48,7 +34,6 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwd
     const cad_scan_args& a = sets.s[blockIdx.z];
     const int lane = threadIdx.x & 63;
     const int wave = cad_uniform(threadIdx.x >> 6);
-    sc_static_priority(wave, SC_W);
     const int64_t sb = blockIdx.y;
     const int e_raw = blockIdx.x * SC_W + wave;
     const bool act = e_raw < a.E;
@@ -69,7 +54,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwd
     const float bias = (a.delta_bias && !is_dt) ? a.delta_bias[e] : 0.f;
     const int64_t nchunks = (L + SC_CHUNK - 1) / SC_CHUNK;
     const int64_t nslots = (L + SC_STATE_STEP - 1) / SC_STATE_STEP;
-    constexpr bool PREF = SC_FWD_DMA && VEC && SC_S * sizeof(T) == 32;
+    constexpr bool PREF = VEC && SC_S * sizeof(T) == 32;
     char* pre = (char*)(smem + RING * 2 * TILE);  // behind the tile ring
     const uint32_t pre_lds = cad_uniform((int)(sc_lds_off(pre) + wave * (64 * 16)));
     // SC_NDMA (= 6) DMA operations per chunk: u, delta, z (u again when there is no gate) x two 16-byte planes
@@ -156,27 +141,18 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwd
         float du[SC_S], dt[SC_S], y[SC_S];
         f32x2 y2[SC_S];  // per item: the output's even-state / odd-state partial sums (one v_pk_fma per item and pair)
         f32x2 dd[SC_S];  // (dt, dt * u)
-#ifndef SC_FWD_PREFETCH
         if constexpr (PREF) {
-            sc_wait_loads<SC_PRE_WAIT ? 2 : 0>();  // this chunk's vectors were fetched into LDS one chunk ago
+            sc_wait_loads<0>();  // this chunk's vectors were fetched into LDS one chunk ago
             read_vector(0, p0, u_raw);
             read_vector(2, p0, d_raw);
         } else if (c > 0) {
             sc_load_raw<T, SC_S, VEC>(u_row, p0, L, rev, u_raw);
             sc_load_raw<T, SC_S, VEC>(d_row, p0, L, rev, d_raw);
         }
-#endif
         sc_by_dir(rev, [&](auto rtag) {  // (one scalar branch per chunk instead of a select + rotate per dword)
             sc_unpack_d<T, SC_S, decltype(rtag)::value != 0>(u_raw, du);
             sc_unpack_d<T, SC_S, decltype(rtag)::value != 0>(d_raw, dt);
         });
-#ifdef SC_FWD_PREFETCH
-        if (z_row) sc_load_raw<T, SC_S, VEC>(z_row, p0, L, rev, z_raw);
-        if (c + 1 < nchunks) {
-            sc_load_raw<T, SC_S, VEC>(u_row, p0 + SC_CHUNK, L, rev, u_raw);
-            sc_load_raw<T, SC_S, VEC>(d_row, p0 + SC_CHUNK, L, rev, d_raw);
-        }
-#endif
         // softplus: a wave-uniform BRANCH around the whole loop when delta already is dt (cad_proj_wx evaluated it); per
         // item it is evaluated for every lane and masked afterwards (a select instead of a branch around the transcendentals;
         // on the vector path a lane's items are in or out of range together)
@@ -204,9 +180,7 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwd
         // (unrolled instantiation: tix = NPC * c + np with NPC a multiple of the ring size, so the slot, the barrier parity and the
         // staging cursor -- which runs AHEAD pairs in front, still inside this chunk at np = 0 -- are functions of np alone)
         if constexpr (NPC != 0) s_np = AHEAD;
-#if SC_FWD_UNROLL_NP
 #pragma unroll
-#endif
         for (int np = 0; np < NP; ++np, ++tix) {
             const int buf = NPC ? (np & (RING - 1)) : (tix & (RING - 1));
             // prefetch the tile AHEAD pairs from now (this chunk's or the next one's)
@@ -280,12 +254,10 @@ __global__ __launch_bounds__(64 * SC_W, SC_OCC_FWD) void scan_fwd_kernel(ScanFwd
         for (int i = 0; i < SC_S; ++i) y[i] = y2[i][0] + y2[i][1];
         if (z_row) {
             float zz[SC_S];
-#ifndef SC_FWD_PREFETCH
             if constexpr (PREF)
                 read_vector(4 + 2 * (int)(c & 1), p0, z_raw);  // landed long ago: the chunk-start wait covered it
             else
                 sc_load_raw<T, SC_S, VEC>(z_row, p0, L, rev, z_raw);
-#endif
             sc_by_dir(rev, [&](auto rtag) { sc_unpack_d<T, SC_S, decltype(rtag)::value != 0>(z_raw, zz); });
 #pragma unroll
             for (int i = 0; i < SC_S; ++i) y[i] *= (SC_WHATIF & 1024) ? zz[i] : zz[i] * cad_sigmoid(zz[i]);
@@ -343,10 +315,10 @@ extern "C" int cad_scan_fwd_multi(const cad_scan_args* sets, int nsets, void* st
     CadProfScope prof(0, stream);
     dim3 grid((unsigned)((a->E + SC_W - 1) / SC_W), (unsigned)a->SB, (unsigned)nsets), block(64 * SC_W);
     const size_t shmem = (size_t)SC_RING_FWD * 2 * SC_TILE(SC_S) * sizeof(float) +
-                         ((SC_FWD_DMA && vec && (a->dtype == CAD_BF16 || a->dtype == CAD_F16) && SC_S == 16) ? PRE_BYTES : 0);
+                         ((vec && (a->dtype == CAD_BF16 || a->dtype == CAD_F16) && SC_S == 16) ? PRE_BYTES : 0);
 #define SC_FWD_LAUNCH(T, V)                                                                  \
     do {                                                                                     \
-        if (SC_FWD_UNROLL_NP && !a->map_only && V && sizeof(T) == 2 && a->N == 2 * SC_FWD_UNROLL_NP) { \
+        if (!a->map_only && V && sizeof(T) == 2 && a->N == 2 * SC_FWD_UNROLL_NP) {           \
             SC_BIG_LDS((scan_fwd_kernel<T, V, false, SC_FWD_UNROLL_NP>), shmem);             \
             CAD_LAUNCH((scan_fwd_kernel<T, V, false, SC_FWD_UNROLL_NP>), grid, block, shmem, stream, ks); \
         } else if (a->map_only) {                                                            \

@@ -331,11 +331,13 @@ def test_fold_kernel_fits_next_to_two_resident_scan_waves(tmp_path):
     wave must fit the 512-entry register file (allocation granule 8) and the two kernels' LDS the 160 KB of a CU -- held on the compiled
     resource usage of the production instantiations (a scan kernel that grows past 232 VGPRs, or a fold kernel past 48, would silently
     serialise the two kernels on the device)."""
-    out = tmp_path / "scan_bwd.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "caduceus_amd", "csrc", "scan_bwd.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
+    asm = ""
+    for src in ("scan_bwd.hip", "scan_fold.hip"):  # the scan kernel / the fold and its placement gate
+        out = tmp_path / (src + ".s")
+        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "-Wno-pass-failed", "-S",
+                               "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "caduceus_amd", "csrc", src)],
+                              stderr=subprocess.DEVNULL)
+        asm += open(out).read()
     res = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S):
         name, body = m.group(1), m.group(2)

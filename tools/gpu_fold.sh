@@ -1,12 +1,12 @@
 #!/bin/bash
-# GPU box: the concurrent dB / dC fold -- parity + stress tests, same-box A/B (fold on the second stream vs fold kernel behind the scan;
-# write-through vs plain slot stores), and a kernel trace of one layer that shows whether the two kernels really overlap.
+# GPU box: the concurrent dB / dC fold -- parity + stress tests, same-box A/B (fold on the second stream vs fold kernel behind the scan),
+# and a kernel trace of one layer that shows whether the two kernels really overlap.
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out/fold
 timeout 900 python -m pytest tests/test_fold_stream.py -m gpu -x -q 2>&1 | tail -5
 timeout 300 python tools/layer_bench.py --ab _STREAM_FOLD --reps 6 --rounds 4 2>&1 | tail -1
-LAYER_BENCH_ARGS="" bash tools/ab_layer.sh 3 default env:CADUCEUS_AMD_STREAM_FOLD=0 nowt,env:CADUCEUS_AMD_STREAM_FOLD=0 | cut -c1-400
+LAYER_BENCH_ARGS="" bash tools/ab_layer.sh 3 default env:CADUCEUS_AMD_STREAM_FOLD=0 | cut -c1-400
 timeout 300 python tools/layer_bench.py --d-model 512 --seqlen 262144 --ab _STREAM_FOLD --reps 3 --rounds 3 2>&1 | tail -1
 timeout 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/fold/trace -o layer -- python tools/layer_bench.py --reps 2 > gpurun_out/fold/trace.log 2>&1
 python - <<'PY'
