@@ -192,6 +192,7 @@ SYMBOLS = {
     "cad_gemm_stream_supported": (_i, [_i64, _i64, _i64, _i]),
     "cad_fold_f32_multi": (_i, [C.POINTER(FoldF32Job), _i, _p]),
     "cad_gemm_f32": (_i, [C.POINTER(GemmF32Args), _p]),
+    "cad_gemm_b16": (_i, [C.POINTER(GemmF32Args), _i, _p]),
     "cad_quant_rows_fp8": (_i, [C.POINTER(QuantFp8Args), _p]),
     "cad_proj_wxT_fp8": (_i, [C.POINTER(ProjFp8Args), _p]),
     "cad_proj_fp8_supported": (_i, [_i]),

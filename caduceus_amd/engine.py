@@ -12,8 +12,10 @@ duplicated in/out projections.  Here:
   * activations between GEMMs and scans are channel-major (E, S*B, L): the in_proj GEMM writes that layout directly
     (W @ X^T) and every scan/conv access is a contiguous run along L.
 
-On THIS (generic, per-op autograd) path the dense projections go through ops.mm (fp32, and fp16 on its exact fp32 widening: the own cad_gemm_f32; bf16: torch.mm / hipBLASLt); the production configuration (tied, "add") runs
-mixer.BiMambaMixerFn instead, whose projections are the library's own MFMA kernels (csrc/gemm.hip) -- no library GEMM on that step.
+On THIS (generic, per-op autograd) path the dense projections go through ops.mm (fp32, and fp16 on its exact fp32 widening: the own
+cad_gemm_f32; bf16: the own strided MFMA GEMM cad_gemm_b16 when _OWN_GEMM_B16 is on, torch.mm / hipBLASLt when it is off -- the kernel has not been timed against the library yet, so the conservative default is off);
+the production configuration (tied, "add") runs mixer.BiMambaMixerFn instead, whose projections are the library's own MFMA kernels
+(csrc/gemm.hip) -- no library GEMM on that step.
 """
 from __future__ import annotations
 
@@ -22,6 +24,12 @@ from typing import Optional
 import torch
 
 from . import mixer, ops, seqpar
+
+# Test and A/B handle (in the style of the mixer's _OWN_* handles): the bf16 products of this engine and of the large-vocabulary LM-head
+# fallbacks (modeling_caduceus.py, modeling_rcps.py) run on the own strided MFMA GEMM (cad_gemm_b16, csrc/gemm_b16.hip) instead of
+# torch.mm / hipBLASLt.  Off by default: the kernel has not been timed against the library yet (DESIGN.md section 9 item 6;
+# tools/gemm_b16_bench.py is the measurement, 0.8 x the library on in_proj and out_proj the rule).
+_OWN_GEMM_B16 = False
 
 
 def _w(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -37,14 +45,14 @@ def _scan_inputs(xz: torch.Tensor, m, split: int, rev_lo: int, rev_hi: int, act:
     N, R = m.d_state, m.dt_rank
     conv = seqpar.causal_conv1d if seqpar.active() else ops.causal_conv1d
     xc = conv(xz[:E], m.conv1d.weight, m.conv1d.bias, split, rev_lo, rev_hi)
-    dbc = ops.mm(_w(m.x_proj.weight, act), xc.view(E, T)).view(R + 2 * N, SB, L)
-    delta = ops.mm(_w(m.dt_proj.weight, act), dbc[:R].reshape(R, T)).view(E, SB, L)
+    dbc = ops.mm(_w(m.x_proj.weight, act), xc.view(E, T), own_b16=_OWN_GEMM_B16).view(R + 2 * N, SB, L)
+    delta = ops.mm(_w(m.dt_proj.weight, act), dbc[:R].reshape(R, T), own_b16=_OWN_GEMM_B16).view(E, SB, L)
     A = -torch.exp(m.A_log.float())
     return (xc, delta, A, dbc[R:R + N], dbc[R + N:], m.D.float(), m.dt_proj.bias.float())
 
 
 def _in_proj(m, x2d: torch.Tensor, SB: int, L: int, act: torch.dtype) -> torch.Tensor:
-    xz = ops.mm(_w(m.in_proj.weight, act), x2d.t())
+    xz = ops.mm(_w(m.in_proj.weight, act), x2d.t(), own_b16=_OWN_GEMM_B16)
     if m.in_proj.bias is not None:
         xz = xz + _w(m.in_proj.bias, act).unsqueeze(1)
     return xz.view(-1, SB, L)
@@ -54,7 +62,7 @@ def _out_proj(m, y: torch.Tensor, acc: Optional[torch.Tensor], act: torch.dtype)
     E = y.shape[0]
     yt = y.view(E, -1).t()
     wt = _w(m.out_proj.weight, act).t()
-    out = ops.mm(yt, wt) if acc is None else ops.addmm(acc, yt, wt)
+    out = ops.mm(yt, wt, own_b16=_OWN_GEMM_B16) if acc is None else ops.addmm(acc, yt, wt, own_b16=_OWN_GEMM_B16)
     if m.out_proj.bias is not None:
         out = out + _w(m.out_proj.bias, act)
     return out

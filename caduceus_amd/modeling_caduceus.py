@@ -352,10 +352,10 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
             else:
                 w = self.lm_head.weight
                 if w.shape[0] <= 16 and getattr(self.lm_head, "bias", None) is None:
-                    logits, loss = ops.lm_head(hidden_t, w, None, labels if fused_loss else None, ignore_index)
+                    logits, loss = ops.lm_head(hidden_t, w, None, labels if fused_loss else None, ignore_index, own_b16=engine._OWN_GEMM_B16)
                 else:
                     h0 = hidden_t[0]
-                    logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t()).view(*h0.shape[:-1], w.shape[0])
+                    logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t(), own_b16=engine._OWN_GEMM_B16).view(*h0.shape[:-1], w.shape[0])
                     if self.lm_head.bias is not None:
                         logits = logits + self.lm_head.bias.to(logits.dtype)
                     logits = logits.float()

@@ -161,16 +161,18 @@ class RCPSLMHead(nn.Module):
         if self.lm_head.bias is not None:
             raise NotImplementedError("RCPSLMHead is bias-free in the reference")
         V = self.lm_head.weight.shape[0]
-        if V > 16:  # large vocabularies: a real GEMM (fp32: cad_gemm_f32; bf16: hipBLASLt)
+        if V > 16:  # large vocabularies: a real GEMM (fp32: cad_gemm_f32; bf16: cad_gemm_b16 behind engine._OWN_GEMM_B16, else hipBLASLt)
             w = self.lm_head.weight.to(hidden.dtype)
             D = hidden.shape[-1]
-            logits = ops.addmm(ops.mm(hidden[0].reshape(-1, D), w.t()), hidden[1].reshape(-1, D), w[self.complement_map].t())
+            own = engine._OWN_GEMM_B16
+            logits = ops.addmm(ops.mm(hidden[0].reshape(-1, D), w.t(), own_b16=own), hidden[1].reshape(-1, D), w[self.complement_map].t(),
+                               own_b16=own)
             logits = logits.view(*hidden.shape[1:-1], V).float()
             loss = None
             if labels is not None:
                 loss = torch.nn.functional.cross_entropy(logits.view(-1, V), labels.view(-1), ignore_index=ignore_index)
             return logits, loss
-        return ops.lm_head(hidden, self.lm_head.weight, self.complement_map, labels, ignore_index)
+        return ops.lm_head(hidden, self.lm_head.weight, self.complement_map, labels, ignore_index, own_b16=engine._OWN_GEMM_B16)
 
     def forward(self, x):
         n_channels = x.shape[-1]

@@ -610,7 +610,7 @@ def selective_scan_stateful(u, delta, A, Bm, Cm, D, z, delta_bias, h0, split: in
 # ------------------------------------------------------------------------------------------------------------------
 class _LmHead(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight, comp, labels, ignore_index):
+    def forward(ctx, hidden, weight, comp, labels, ignore_index, own_b16=False):
         hidden = hidden.contiguous()
         S, D = hidden.shape[0], hidden.shape[-1]
         rows = hidden.numel() // (S * D)
@@ -629,7 +629,7 @@ class _LmHead(torch.autograd.Function):
         L.check(L.get_lib().cad_lm_head_fwd(C.byref(a), stream), "cad_lm_head_fwd")
         loss = acc[0] / acc[1] if labels is not None else acc[0]
         ctx.save_for_backward(hidden, w, comp, lab, logits, acc)
-        ctx.meta = (ignore_index, weight.dtype, labels is not None)
+        ctx.meta = (ignore_index, weight.dtype, labels is not None, bool(own_b16))
         # an output nobody differentiated reaches backward as None instead of a zero-filled (rows, V) fp32 tensor the kernel would
         # allocate and read (training uses the loss alone)
         ctx.set_materialize_grads(False)
@@ -638,7 +638,7 @@ class _LmHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dloss):
         hidden, w, comp, lab, logits, acc = ctx.saved_tensors
-        ignore_index, wdt, has_labels = ctx.meta
+        ignore_index, wdt, has_labels, own = ctx.meta
         S, D = hidden.shape[0], hidden.shape[-1]
         V = w.shape[0]
         lib = L.get_lib()
@@ -661,7 +661,7 @@ class _LmHead(torch.autograd.Function):
                                     L.ptr(logits), L.ptr(dlg), L.ptr(coef), dh.data_ptr() + c0 * es, parts.data_ptr() + c0 * 4, rows, DB, V, S,
                                     int(ignore_index), L.dtype_code(hidden.dtype), 0 if DB == D else D)
                 L.check(lib.cad_lm_head_bwd(C.byref(a), stream), "cad_lm_head_bwd")
-            return dh, parts.sum(dim=0).to(wdt), None, None, None
+            return dh, parts.sum(dim=0).to(wdt), None, None, None, None
         # (other shapes: torch ops)
         # d loss / d logits = (softmax - onehot) * valid / count, assembled WITHOUT boolean-mask indexing: `sm[rows[valid], lab[valid]]`
         # goes through nonzero(), i.e. a device-to-host copy in the middle of the backward -- the launch queue ran dry behind it
@@ -681,19 +681,20 @@ class _LmHead(torch.autograd.Function):
         h = hidden.reshape(S, -1, D)
         dh = torch.empty_like(h)
         wt = w.to(hidden.dtype)
-        dh[0] = mm(gt, wt)
-        dw = mm(gt.t(), h[0]).float()
+        dh[0] = mm(gt, wt, own_b16=own)
+        dw = mm(gt.t(), h[0], own_b16=own).float()
         if S == 2:
-            dh[1] = mm(gt, wt[comp])
-            d2 = mm(gt.t(), h[1]).float()
+            dh[1] = mm(gt, wt[comp], own_b16=own)
+            d2 = mm(gt.t(), h[1], own_b16=own).float()
             dw.index_add_(0, comp, d2)
-        return dh.reshape(hidden.shape), dw.to(wdt), None, None, None
+        return dh.reshape(hidden.shape), dw.to(wdt), None, None, None, None
 
 
 def lm_head(hidden: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor],
-            labels: Optional[torch.Tensor] = None, ignore_index: int = -100):
-    """hidden: (S, B, L, D) t-frame -> (fp32 logits (B, L, V), loss or None).  RCPSLMHead + cross_entropy."""
-    logits, loss = _LmHead.apply(hidden, weight, comp, labels, ignore_index)
+            labels: Optional[torch.Tensor] = None, ignore_index: int = -100, own_b16: bool = False):
+    """hidden: (S, B, L, D) t-frame -> (fp32 logits (B, L, V), loss or None).  RCPSLMHead + cross_entropy.
+    own_b16: the backward's torch-op branch (shapes cad_lm_head_bwd does not take) multiplies bf16 on cad_gemm_b16, not the library."""
+    logits, loss = _LmHead.apply(hidden, weight, comp, labels, ignore_index, own_b16)
     return logits, (loss if labels is not None else None)
 
 
@@ -753,12 +754,18 @@ def bmm_f32(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
 
 
 def _gemm_f32(a, b, out, addend):
-    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 3 or b.dim() != 3:
-        raise ValueError("gemm_f32: fp32 operands, (n, M, K) @ (n, K, N)")
+    return _gemm_strided("gemm_f32", torch.float32, torch.float32, a, b, out, addend)
+
+
+def _gemm_strided(name, in_dtype, out_dtype, a, b, out, addend):
+    """The launch of cad_gemm_f32 (fp32 operands) and cad_gemm_b16 (bf16 operands; bf16 result, or out_dtype fp32: its out_f32 form): one
+    argument struct, one stride normalisation."""
+    if a.dtype != in_dtype or b.dtype != in_dtype or a.dim() != 3 or b.dim() != 3:
+        raise ValueError(f"{name}: {in_dtype} operands, (n, M, K) @ (n, K, N)")
     n, M, K = a.shape
     N = b.shape[2]
     if b.shape[0] != n or b.shape[1] != K:
-        raise ValueError(f"gemm_f32: shapes {tuple(a.shape)} @ {tuple(b.shape)}")
+        raise ValueError(f"{name}: shapes {tuple(a.shape)} @ {tuple(b.shape)}")
 
     def strides(t):
         """(row, column) element strides the kernel needs: one of them 1.  The stride of a size-1 dimension is never used: report it as
@@ -772,17 +779,17 @@ def _gemm_f32(a, b, out, addend):
             t = t.contiguous()
             rs, cs = t.stride(1), t.stride(2)
             if cs != 1:  # (n, M, 1) contiguous: strides (M, 1, 1) -- cannot happen; kept as a guard
-                raise ValueError("gemm_f32: operand without a unit stride")
+                raise ValueError(f"{name}: operand without a unit stride")
         return t, rs, cs
 
     a, a_rs, a_cs = strides(a)
     b, b_rs, b_cs = strides(b)
     if out is None:
-        out = torch.empty((n, M, N), dtype=torch.float32, device=a.device)
-    if out.dtype != torch.float32 or tuple(out.shape) != (n, M, N):
-        raise ValueError("gemm_f32: out must be fp32 (n, M, N)")
-    if addend is not None and (addend.dtype != torch.float32 or addend.shape != out.shape or addend.stride() != out.stride()):
-        raise ValueError("gemm_f32: addend must have out's dtype, shape and strides")
+        out = torch.empty((n, M, N), dtype=out_dtype, device=a.device)
+    if out.dtype != out_dtype or tuple(out.shape) != (n, M, N):
+        raise ValueError(f"{name}: out must be {out_dtype} (n, M, N)")
+    if addend is not None and (addend.dtype != out_dtype or addend.shape != out.shape or addend.stride() != out.stride()):
+        raise ValueError(f"{name}: addend must have out's dtype, shape and strides")
     if M == 0 or N == 0:
         return out
     if K == 0:
@@ -791,11 +798,14 @@ def _gemm_f32(a, b, out, addend):
         elif addend.data_ptr() != out.data_ptr():
             out.copy_(addend)
         return out
-    stream = L.stream_and_check(a, b, out, contiguous=False)
+    stream = L.stream_and_check(a, b, out, addend, contiguous=False)
     bs = lambda t: t.stride(0) if n > 1 else 0
     args = L.GemmF32Args(L.ptr(a), L.ptr(b), L.ptr(out), None if addend is None else L.ptr(addend), M, N, K,
                          a_rs, a_cs, b_rs, b_cs, max(out.stride(1), 1), max(out.stride(2), 1), n, bs(a), bs(b), bs(out))
-    L.check(L.get_lib().cad_gemm_f32(C.byref(args), stream), "cad_gemm_f32")
+    if in_dtype == torch.float32:
+        L.check(L.get_lib().cad_gemm_f32(C.byref(args), stream), "cad_gemm_f32")
+    else:
+        L.check(L.get_lib().cad_gemm_b16(C.byref(args), int(out_dtype == torch.float32), stream), "cad_gemm_b16")
     return out
 
 
@@ -841,10 +851,67 @@ class _MmF16(torch.autograd.Function):
         return da, db, (g if ctx.needs_input_grad[2] else None)
 
 
-def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def mm_b16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (M, N) bf16 = [addend +] a (M, K) @ b (K, N) of bf16 operands on cad_gemm_b16 (csrc/gemm_b16.hip): fp32 accumulation, the sum
+    (plus the widened addend) rounded ONCE to bf16.  Views as for mm_f32: one unit stride per operand, any pitch, any 2-D bf16 view as
+    out.  A product with a small result and a long reduction (an engine weight gradient with K = S * B * L tokens) is cut into K slices
+    by mm_f32's rule: ONE batched launch with fp32 partial tiles (the kernel's out_f32 form), summed by fold_f32, rounded once."""
+    if a.dim() != 2 or b.dim() != 2:
+        raise ValueError("mm_b16: 2-D operands")
+    M, K = a.shape
+    N = b.shape[1]
+    n = _f32_kslices(M, N, K) if b.shape[0] == K else 1  # (a shape mismatch is reported by _gemm_strided)
+    if n > 1:
+        Kc = K // n
+        part = _gemm_strided("gemm_b16", torch.bfloat16, torch.float32, a.unflatten(1, (n, Kc)).permute(1, 0, 2), b.unflatten(0, (n, Kc)),
+                             None, None)  # (n, M, N) fp32
+        res = torch.empty((M, N), dtype=torch.float32, device=a.device)
+        if (M * N) % 4 == 0:
+            fold_f32([(part, res, M * N, n, M * N, 1, 0)])
+        else:
+            torch.sum(part, dim=0, out=res)
+        if addend is not None:
+            res = res + addend.float()
+        if out is None:
+            return res.to(torch.bfloat16)
+        out.copy_(res)
+        return out
+    return _gemm_strided("gemm_b16", torch.bfloat16, torch.bfloat16, a.unsqueeze(0), b.unsqueeze(0), None if out is None else out.unsqueeze(0),
+                         None if addend is None else addend.unsqueeze(0))[0]
+
+
+def bmm_b16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """out (n, M, N) = a (n, M, K) @ b (n, K, N) of bf16 operands, one launch (cad_gemm_b16, blockIdx.z = batch); out_f32: the fp32 sums
+    instead of their bf16 rounding."""
+    return _gemm_strided("gemm_b16", torch.bfloat16, torch.float32 if out_f32 else torch.bfloat16, a, b, out, None)
+
+
+class _MmB16(torch.autograd.Function):
+    """a @ b (+ addend) of bf16 operands on cad_gemm_b16, differentiable: da = g @ b^T, db = a^T @ g through the same kernel (transposed
+    views; a weight gradient over all tokens takes mm_b16's K slices)."""
+
+    @staticmethod
+    def forward(ctx, a, b, addend):
+        ctx.save_for_backward(a, b)
+        return mm_b16(a, b, addend=None if addend is None else addend.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        da = mm_b16(g, b.t()) if ctx.needs_input_grad[0] else None
+        db = mm_b16(a.t(), g) if ctx.needs_input_grad[1] else None
+        return da, db, (g if ctx.needs_input_grad[2] else None)
+
+
+def _b16(*ts) -> bool:
+    return all(t.dtype == torch.bfloat16 for t in ts)
+
+
+def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, own_b16: bool = False) -> torch.Tensor:
     """torch.mm for the call sites that have no dedicated kernel: fp32 operands take the own fp32 matrix-core kernel (cad_gemm_f32;
     differentiable), fp16 operands the same kernel on their exact fp32 widening (fp16 result), bf16 shapes the MFMA projection kernels
-    do not serve the library."""
+    do not serve the library -- or, for a call site that asks for it (own_b16: the generic engine, the LM-head fallbacks), the own bf16
+    kernel (cad_gemm_b16; differentiable)."""
     if _own_f32(a, b):
         if out is not None:
             return mm_f32(a, b, out=out)
@@ -853,15 +920,22 @@ def mm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
         if out is not None:
             return out.copy_(mm_f32(a.float(), b.float()))
         return _MmF16.apply(a, b, None)
+    if own_b16 and _b16(a, b):
+        if out is not None:
+            return mm_b16(a, b, out=out)
+        return _MmB16.apply(a, b, None)
     return torch.mm(a, b) if out is None else torch.mm(a, b, out=out)
 
 
-def addmm(acc: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """acc + a @ b (torch.addmm), fp32 / fp16 on the own kernel."""
+def addmm(acc: torch.Tensor, a: torch.Tensor, b: torch.Tensor, own_b16: bool = False) -> torch.Tensor:
+    """acc + a @ b (torch.addmm), fp32 / fp16 on the own kernel; bf16 on the library, or (own_b16, as for mm) on cad_gemm_b16 with the
+    addend inside the one rounding."""
     if _own_f32(acc, a, b):
         return _MmF32.apply(a, b, acc)
     if _f16(acc, a, b):
         return _MmF16.apply(a, b, acc)
+    if own_b16 and _b16(acc, a, b):
+        return _MmB16.apply(a, b, acc)
     return torch.addmm(acc, a, b)
 
 

@@ -377,7 +377,7 @@ int64_t cad_scan_bwd_fold_counter_ints(int64_t SB, int64_t L);
  * ROUNDING CONTRACT of every 16-bit projection below (bf16 and fp16 alike): the K products of an output element are exact in fp32 and
  * summed in fp32 (the MFMA accumulators, over all of K and over both panels of cad_proj_xTw), and that fp32 sum is rounded ONCE, to
  * nearest even, to the output type; a finite sum beyond the output type's range gives +-inf, NaN / inf operands propagate to exactly the
- * output elements they enter.  fp32 outputs (weight-gradient slots, CAD_GEMM_PARTIALS tiles, cad_gemm_f32) are the fp32 sums themselves.
+ * output elements they enter.  fp32 outputs (weight-gradient slots, CAD_GEMM_PARTIALS tiles, cad_gemm_f32, cad_gemm_b16's out_f32 form) are the fp32 sums themselves.
  * The two addend forms differ, see cad_proj_wx: thin M / deep K adds the widened addend to the fp32 sum BEFORE the one rounding; thin K
  * rounds the product first and rounds again after the addition. */
 typedef struct {
@@ -522,6 +522,16 @@ typedef struct {
     int64_t batch, a_bs, b_bs, d_bs;
 } cad_gemm_f32_args;
 int cad_gemm_f32(const cad_gemm_f32_args* a, void* stream);
+/* cad_gemm_b16: the same product for bf16 operands on v_mfma_f32_16x16x32_bf16 -- the projections of the generic per-op engine
+ * (un-tied, ew_multiply and uni-directional configurations) and their gradients in bf16, under the ROUNDING CONTRACT above.  It takes the
+ * struct of cad_gemm_f32 as it is; for THIS entry point `A` and `B` address bf16 elements, and so do `D` and `addend` unless out_f32 (the
+ * float pointer types are not meant: pass the bf16 base pointers).  All strides, the batch strides included, count ELEMENTS of the
+ * respective type.  out_f32 = 0: the fp32 sum over all of K, plus the widened bf16 addend if one is given, is rounded ONCE to bf16.
+ * out_f32 = 1: D and addend are fp32 and D holds the fp32 sums themselves (the K slices of a weight gradient over all tokens as one
+ * batched launch; the caller sums the partial tiles in fp32 and rounds once).  Operands need 2-byte alignment only (16-byte vector loads
+ * are used where base, pitch and offset allow them); addend (optional, may be D itself) is addressed with D's strides d_rs, d_cs and
+ * d_bs; any M, N, K >= 1; the (M, N) tile index runs on grid.x, so M is not capped. */
+int cad_gemm_b16(const cad_gemm_f32_args* a, int out_f32, void* stream);
 int cad_gemm_stream_supported(int64_t R, int64_t C, int64_t K, int nslices);
 
 /* ---------------------------------------------------------------------------------------------------------
