@@ -11,10 +11,12 @@ from .modeling_rcps import RCPSAddNormWrapper, RCPSEmbedding, RCPSLMHead, RCPSMa
 from .tokenization_caduceus import CaduceusTokenizer
 from .downstream import DNAEmbeddingModelCaduceus, SequenceDecoder
 from .mamba import fp16_kernels
+from .generation import InferenceParams, decode_step, generate
 
 __all__ = ["DNAEmbeddingModelCaduceus", "SequenceDecoder", "CaduceusConfig", "Caduceus", "CaduceusForMaskedLM", "CaduceusForSequenceClassification",
            "CaduceusTokenizer", "CaduceusMixerModel", "BiMambaWrapper", "create_block", "RCPSEmbedding", "RCPSWrapper",
-           "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "fp16_kernels", "register_auto_classes"]
+           "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "fp16_kernels", "register_auto_classes", "InferenceParams",
+           "decode_step", "generate"]
 
 
 def register_auto_classes():

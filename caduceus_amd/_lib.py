@@ -124,6 +124,12 @@ class ProjFp8Args(C.Structure):
                 ("ldw", _i64), ("ldx", _i64), ("ldo", _i64)]
 
 
+class MambaStepArgs(C.Structure):
+    _fields_ = [("h", _p), ("out", _p), ("conv_state", _p), ("ssm_state", _p), ("W_in", _p), ("b_in", _p), ("conv_w", _p), ("conv_b", _p),
+                ("W_x", _p), ("W_dt", _p), ("dt_bias", _p), ("A_log", _p), ("Dskip", _p), ("W_out", _p), ("b_out", _p), ("scratch", _p),
+                ("B", _i64), ("D", _i), ("E", _i), ("N", _i), ("R", _i), ("K", _i), ("dtype", _i)]
+
+
 class LmHeadArgs(C.Structure):
     _fields_ = [("hidden", _p), ("weight", _p), ("comp", _p), ("labels", _p), ("logits", _p), ("loss_sum", _p),
                 ("count", _p), ("rows", _i64), ("D", _i), ("V", _i), ("n_strands", _i), ("ignore_index", _i64),
@@ -196,6 +202,9 @@ SYMBOLS = {
     "cad_quant_rows_fp8": (_i, [C.POINTER(QuantFp8Args), _p]),
     "cad_proj_wxT_fp8": (_i, [C.POINTER(ProjFp8Args), _p]),
     "cad_proj_fp8_supported": (_i, [_i]),
+    "cad_mamba_step": (_i, [C.POINTER(MambaStepArgs), _p]),
+    "cad_mamba_step_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "cad_mamba_step_scratch_floats": (_i64, [_i64, _i, _i, _i]),
     "cad_lm_head_fwd": (_i, [C.POINTER(LmHeadArgs), _p]),
     "cad_lm_head_partials": (_i64, [_i64]),
     "cad_lm_head_bwd": (_i, [C.POINTER(LmHeadBwdArgs), _p]),

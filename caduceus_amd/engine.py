@@ -134,3 +134,35 @@ def from_tframe(t: torch.Tensor) -> torch.Tensor:
     if t.shape[0] == 1:
         return t[0]
     return torch.cat([t[0], t[1].flip(-1)], dim=-1)
+
+
+# ---- the left-to-right mixer with a step-wise inference cache (mamba.Mamba.forward with `inference_params`) -----------------------
+
+def mamba_prefill(hn: torch.Tensor, m, conv_state: torch.Tensor, ssm_state: torch.Tensor, cont: bool) -> torch.Tensor:
+    """One left-to-right Mamba `m` over hn (B, L, D) in the compute dtype, leaving the cache behind it (inference only).
+    cont=False: a prefill from empty states.  cont=True: the next chunk of a prefill -- the d_conv - 1 cached columns are the conv
+    halo and ssm_state enters the scan as h0.  conv_state (>= B, E, d_conv) and ssm_state (>= B, E, N) are refreshed in rows [0, B):
+    the last d_conv columns of x (zero-padded on the left while fewer exist) and the scan's hT."""
+    B, L, D = hn.shape
+    act = hn.dtype
+    N, R, K = m.d_state, m.dt_rank, m.d_conv
+    xz = _in_proj(m, hn.reshape(B * L, D), B, L, act)
+    E = xz.shape[0] // 2
+    x = xz[:E]
+    halo = K - 1 if cont else 0
+    xin = torch.cat([conv_state[:B, :, 1:].permute(1, 0, 2), x], dim=2) if halo else x
+    xc = ops.causal_conv1d(xin, m.conv1d.weight, m.conv1d.bias, B, 0, 1)
+    if halo:  # (positions the halo itself produced saw a zero left pad: dropped)
+        xc = xc[:, :, halo:].contiguous()
+    T = B * L
+    dbc = ops.mm(_w(m.x_proj.weight, act), xc.view(E, T), own_b16=_OWN_GEMM_B16).view(R + 2 * N, B, L)
+    delta = ops.mm(_w(m.dt_proj.weight, act), dbc[:R].reshape(R, T), own_b16=_OWN_GEMM_B16).view(E, B, L)
+    h0 = ssm_state[:B].permute(1, 0, 2).contiguous() if cont else None
+    y, hT = ops.selective_scan_stateful(xc, delta, -torch.exp(m.A_log.float()), dbc[R:R + N], dbc[R + N:], m.D.float(), xz[E:],
+                                        m.dt_proj.bias.float(), h0, B, 0, 1)
+    ssm_state[:B].copy_(hT.permute(1, 0, 2))
+    window = torch.cat([conv_state[:B].permute(1, 0, 2), x], dim=2) if cont else x
+    if window.shape[2] < K:
+        window = torch.nn.functional.pad(window, (K - window.shape[2], 0))
+    conv_state[:B].copy_(window[:, :, -K:].permute(1, 0, 2))
+    return _out_proj(m, y, None, act).view(B, L, D)

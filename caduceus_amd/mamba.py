@@ -70,6 +70,12 @@ def as_requested(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return t.to(torch.float16) if requested_dtype(x) == torch.float16 else t
 
 
+# The reference passes `inference_params` through its bi-directional and RCPS wrappers and lets both directions share one cache
+# (modeling_caduceus.py:122-132, modeling_rcps.py:201-206); that is not a decode step of anything, so it is not restated here.
+NO_STEPWISE_FORM = ("step-wise decoding needs a causal stack (bidirectional=False, rcps=False): a right-to-left direction has no "
+                    "step-wise form, every new token would change the state at every earlier position")
+
+
 class Mamba(nn.Module):
     """Parameter container + single-direction forward with the signature of mamba_ssm.modules.mamba_simple.Mamba."""
 
@@ -112,15 +118,65 @@ class Mamba(nn.Module):
         self.out_proj = nn.Linear(self.d_inner, d_model, bias=bias, **factory_kwargs)
 
     def forward(self, hidden_states, inference_params=None):
-        """hidden_states: (B, L, D) -> (B, L, D), left-to-right."""
-        if inference_params is not None:
-            raise NotImplementedError("step-wise inference cache is outside the pre-training hot path")
+        """hidden_states: (B, L, D) -> (B, L, D), left-to-right.  With `inference_params` (generation.InferenceParams) the layer's
+        (conv_state, ssm_state) are looked up by layer_idx in its key_value_memory_dict (allocated on first use) and left up to date:
+        seqlen_offset == 0 is a prefill, seqlen_offset > 0 with L == 1 one `step`, with L > 1 the next chunk of a prefill."""
+        if inference_params is None:
+            act = act_dtype_of(hidden_states)
+            out = engine.bimamba_tframe(hidden_states.to(act).unsqueeze(0), self, None, None, strand_swap=False)
+            return as_requested(out[0], hidden_states)
+        B, L, _ = hidden_states.shape
         act = act_dtype_of(hidden_states)
-        out = engine.bimamba_tframe(hidden_states.to(act).unsqueeze(0), self, None, None, strand_swap=False)
-        return as_requested(out[0], hidden_states)
+        conv_state, ssm_state = self._get_states_from_cache(inference_params, B, act)
+        if inference_params.seqlen_offset > 0 and L == 1:
+            return self.step(hidden_states, conv_state, ssm_state)[0]
+        dev = hidden_states.device.type
+        with torch.no_grad(), torch.autocast(dev, enabled=False):  # (the compute dtype is decided: see engine.bimamba_tframe)
+            out = engine.mamba_prefill(hidden_states.to(act), self, conv_state, ssm_state, cont=inference_params.seqlen_offset > 0)
+        return as_requested(out, hidden_states)
+
+    def step(self, hidden_states, conv_state, ssm_state):
+        """mamba_ssm `Mamba.step`: one token hidden_states (B, 1, D) -> (out (B, 1, D), conv_state, ssm_state), the two states updated
+        in place in their first B rows.  Runs the step kernels (ops.mamba_step) on the fp32 master parameters."""
+        B, L, _ = hidden_states.shape
+        if L != 1:
+            raise ValueError("Only support decoding with 1 token at a time for now")
+        act = act_dtype_of(hidden_states)
+        if conv_state.dtype != act:
+            raise TypeError(f"conv_state is {conv_state.dtype} but this call computes in {act}: allocate the cache with dtype={act}")
+        need = (B, self.d_inner, self.d_state, self.dt_rank)
+        scratch = getattr(self, "_step_scratch", None)
+        if scratch is None or scratch[0] != need or scratch[1].device != hidden_states.device:
+            scratch = (need, ops.mamba_step_scratch(*need, hidden_states.device))
+            self._step_scratch = scratch  # (a plain attribute: not a buffer, never saved)
+        f = lambda p: None if p is None else p.float()
+        with torch.no_grad():
+            out = ops.mamba_step(hidden_states[:, 0].to(act).contiguous(), conv_state, ssm_state, f(self.in_proj.weight),
+                                 f(self.in_proj.bias), f(self.conv1d.weight), f(self.conv1d.bias), f(self.x_proj.weight),
+                                 f(self.dt_proj.weight), f(self.dt_proj.bias), f(self.A_log), f(self.D), f(self.out_proj.weight),
+                                 f(self.out_proj.bias), scratch[1], act)
+        return as_requested(out.unsqueeze(1), hidden_states), conv_state, ssm_state
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
-        raise NotImplementedError("step-wise inference cache is outside the pre-training hot path")
+        """(conv_state (B, E, d_conv) in `dtype`, ssm_state (B, E, N) fp32), zeroed.  dtype: the compute dtype of the calls that will
+        use the cache (default: the parameters' dtype; under bf16 autocast pass torch.bfloat16)."""
+        device = self.out_proj.weight.device
+        conv_dtype = self.conv1d.weight.dtype if dtype is None else dtype
+        conv_state = torch.zeros(batch_size, self.d_inner, self.d_conv, device=device, dtype=conv_dtype)
+        ssm_state = torch.zeros(batch_size, self.d_inner, self.d_state, device=device, dtype=torch.float32)
+        return conv_state, ssm_state
+
+    def _get_states_from_cache(self, inference_params, batch_size, act):
+        if self.layer_idx is None:
+            raise ValueError("a Mamba that is used with inference_params needs a layer_idx")
+        kv = inference_params.key_value_memory_dict
+        if self.layer_idx not in kv:  # allocated on first use, as upstream does -- in the compute dtype of this call
+            kv[self.layer_idx] = self.allocate_inference_cache(max(batch_size, inference_params.max_batch_size),
+                                                               inference_params.max_seqlen, dtype=act)
+        conv_state, ssm_state = kv[self.layer_idx]
+        if conv_state.shape[0] < batch_size:
+            raise ValueError(f"the inference cache holds {conv_state.shape[0]} rows, the batch has {batch_size}")
+        return conv_state, ssm_state
 
 
 class RMSNorm(nn.Module):
@@ -188,6 +244,12 @@ class Block(nn.Module):
         if h.dtype not in (torch.float32, act):
             h = h.to(act)
         r = None if residual is None else residual.unsqueeze(0).float()
+        if inference_params is not None:  # the cached path: add + norm as always, then the mixer with its cache
+            getattr(self.mixer, "_require_stepwise", lambda: None)()  # (a bi-directional mixer raises before any launch)
+            w, b, eps, is_rms = norm_params(self.norm)
+            with torch.no_grad():
+                hn, res = ops.add_norm(h, r, w, b, eps, is_rms, False, act)
+            return as_requested(self.mixer(hn[0], inference_params=inference_params), hidden_states), res[0]
         out, res = self.forward_tframe(h, r, act)
         return as_requested(out[0], hidden_states), res[0]
 

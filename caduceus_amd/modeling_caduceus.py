@@ -19,7 +19,7 @@ from transformers.modeling_outputs import BaseModelOutputWithNoAttention, Masked
 from . import engine, ops
 from . import mixer as mixer_sched
 from .configuration_caduceus import CaduceusConfig
-from .mamba import Block, Mamba, RMSNorm, act_dtype_of, as_requested, fp16_kernels, norm_params
+from .mamba import NO_STEPWISE_FORM, Block, Mamba, RMSNorm, act_dtype_of, as_requested, fp16_kernels, norm_params
 from .modeling_rcps import RCPSAddNormWrapper, RCPSEmbedding, RCPSLMHead, RCPSMambaBlock, RCPSWrapper
 
 
@@ -80,12 +80,18 @@ class BiMambaWrapper(nn.Module):
     def forward(self, hidden_states, inference_params=None):
         """hidden_states: (B, L, D) -> same shape."""
         if inference_params is not None:
-            raise NotImplementedError("step-wise inference cache is outside the pre-training hot path")
+            self._require_stepwise()
+            return self.mamba_fwd(hidden_states, inference_params=inference_params)
         act = act_dtype_of(hidden_states)
         return as_requested(self.forward_tframe(hidden_states.to(act).unsqueeze(0), strand_swap=False)[0], hidden_states)
 
-    def allocate_inference_cache(self, *args, **kwargs):
-        raise NotImplementedError("step-wise inference cache is outside the pre-training hot path")
+    def _require_stepwise(self):
+        if self.bidirectional:
+            raise NotImplementedError(NO_STEPWISE_FORM)
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        self._require_stepwise()
+        return self.mamba_fwd.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
 
 
 class CaduceusEmbeddings(nn.Module):
@@ -164,8 +170,40 @@ class CaduceusMixerModel(nn.Module):
             collect.append(hidden)
         return hidden
 
-    def forward(self, input_ids, inputs_embeds=None, output_hidden_states=False):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        """{layer_idx: (conv_state, ssm_state)} of a causal stack (mamba_ssm MixerModel.allocate_inference_cache)."""
+        self._require_stepwise()
+        return {i: layer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs) for i, layer in enumerate(self.layers)}
+
+    def _require_stepwise(self):
+        if self.rcps or any(not isinstance(layer.mixer, BiMambaWrapper) or layer.mixer.bidirectional for layer in self.layers):
+            raise NotImplementedError(NO_STEPWISE_FORM)
+
+    def forward_tframe_cached(self, input_ids, inputs_embeds, inference_params) -> torch.Tensor:
+        """forward_tframe of a causal stack through the step-wise cache: a prefill (seqlen_offset == 0), one decode token, or the next
+        chunk of a prefill.  The residual stream stays fp32; a decode token's add + norm is ops.add_norm on (1, B, 1, D).  The caller
+        advances inference_params.seqlen_offset."""
+        self._require_stepwise()
+        with torch.no_grad():
+            if inputs_embeds is not None:
+                act = act_dtype_of(inputs_embeds)
+                hidden = inputs_embeds if inputs_embeds.dtype in (torch.float32, act) else inputs_embeds.to(act)
+            else:
+                w = self.embeddings.word_embeddings.weight
+                act = act_dtype_of(w)
+                hidden = self.embeddings.forward_tframe(input_ids, torch.float32 if w.dtype == torch.float32 else act)[0]
+            residual = None
+            for layer in self.layers:
+                hidden, residual = layer(hidden, residual, inference_params=inference_params)
+            w, b, eps, is_rms = norm_params(self.norm_f)
+            hidden, _ = ops.add_norm(hidden.unsqueeze(0), residual.unsqueeze(0), w, b, eps, is_rms, False, act)
+        return hidden
+
+    def forward(self, input_ids, inputs_embeds=None, output_hidden_states=False, inference_params=None):
         """Mixer forward: returns (hidden_states (B, L, 2D | D), all_hidden_states)."""
+        if inference_params is not None:
+            like = inputs_embeds if inputs_embeds is not None else self.embeddings.word_embeddings.weight
+            return as_requested(self.forward_tframe_cached(input_ids, inputs_embeds, inference_params)[0], like), []
         collect = [] if output_hidden_states else None
         hidden = self.forward_tframe(input_ids, inputs_embeds, collect)
         like = inputs_embeds if inputs_embeds is not None else self.embeddings.word_embeddings.weight
@@ -333,6 +371,20 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
     def set_decoder(self, decoder):
         self.caduceus = decoder
 
+    def logits_tframe(self, hidden_t, labels, ignore_index):
+        """(fp32 logits, loss | None) of the final t-frame hidden state (S, B, L, D); labels: fused cross entropy, or None."""
+        if self.config.rcps:
+            return self.lm_head.forward_tframe(hidden_t, labels, ignore_index)
+        w = self.lm_head.weight
+        if w.shape[0] <= 16 and getattr(self.lm_head, "bias", None) is None:
+            return ops.lm_head(hidden_t, w, None, labels, ignore_index, own_b16=engine._OWN_GEMM_B16)
+        h0 = hidden_t[0]
+        logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t(), own_b16=engine._OWN_GEMM_B16).view(*h0.shape[:-1], w.shape[0])
+        if self.lm_head.bias is not None:
+            logits = logits + self.lm_head.bias.to(logits.dtype)
+        logits = logits.float()
+        return logits, (cross_entropy(logits, labels, ignore_index=ignore_index) if labels is not None else None)
+
     def forward(self, input_ids: torch.LongTensor = None, inputs_embeds: Optional[torch.FloatTensor] = None,
                 labels: Optional[torch.LongTensor] = None, loss_weights: Optional[torch.FloatTensor] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None,
@@ -347,19 +399,7 @@ class CaduceusForMaskedLM(CaduceusPreTrainedModel):
             ignore_index = getattr(self.config, "pad_token_id", None)
             ignore_index = -100 if ignore_index is None else ignore_index
             fused_loss = labels is not None and loss_weights is None
-            if self.config.rcps:
-                logits, loss = self.lm_head.forward_tframe(hidden_t, labels if fused_loss else None, ignore_index)
-            else:
-                w = self.lm_head.weight
-                if w.shape[0] <= 16 and getattr(self.lm_head, "bias", None) is None:
-                    logits, loss = ops.lm_head(hidden_t, w, None, labels if fused_loss else None, ignore_index, own_b16=engine._OWN_GEMM_B16)
-                else:
-                    h0 = hidden_t[0]
-                    logits = ops.mm(h0.reshape(-1, h0.shape[-1]), w.to(hidden_t.dtype).t(), own_b16=engine._OWN_GEMM_B16).view(*h0.shape[:-1], w.shape[0])
-                    if self.lm_head.bias is not None:
-                        logits = logits + self.lm_head.bias.to(logits.dtype)
-                    logits = logits.float()
-                    loss = cross_entropy(logits, labels, ignore_index=ignore_index) if fused_loss else None
+            logits, loss = self.logits_tframe(hidden_t, labels if fused_loss else None, ignore_index)
             if labels is not None and loss_weights is not None:
                 loss = weighted_cross_entropy(logits, labels, loss_weights, ignore_index=ignore_index)
             all_hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None

@@ -11,7 +11,7 @@ import torch
 from torch import Tensor, nn
 
 from . import engine, ops
-from .mamba import RMSNorm, act_dtype_of, as_requested, norm_params
+from .mamba import NO_STEPWISE_FORM, RMSNorm, act_dtype_of, as_requested, norm_params
 
 
 def _comp_tensor(complement_map: dict) -> Tensor:
@@ -68,6 +68,8 @@ class RCPSWrapper(nn.Module):
         return self.submodule.forward_tframe(hn, strand_swap=True)
 
     def forward(self, x, **kwargs):
+        if kwargs.get("inference_params") is not None:  # the reverse-complement strand runs right-to-left
+            raise NotImplementedError(NO_STEPWISE_FORM)
         if hasattr(self.submodule, "forward_tframe"):
             kwargs.pop("inference_params", None)
             act = act_dtype_of(x)
@@ -78,7 +80,7 @@ class RCPSWrapper(nn.Module):
         return torch.cat([fwd_out, self.rc(rc_out)], dim=-1)
 
     def allocate_inference_cache(self, *args, **kwargs):
-        return self.submodule.allocate_inference_cache(*args, **kwargs)
+        raise NotImplementedError(NO_STEPWISE_FORM)
 
 
 class RCPSAddNormWrapper(RCPSWrapper):
@@ -128,6 +130,8 @@ class RCPSMambaBlock(nn.Module):
 
     def forward(self, hidden_states: Tensor, residual: Optional[Tensor] = None, inference_params=None):
         """(B, L, 2D) x2 -> (hidden, residual) like the reference (residual is returned in fp32)."""
+        if inference_params is not None:
+            raise NotImplementedError(NO_STEPWISE_FORM)
         act = act_dtype_of(hidden_states)
         h = engine.to_tframe(hidden_states, True)
         if h.dtype not in (torch.float32, act):
@@ -137,7 +141,7 @@ class RCPSMambaBlock(nn.Module):
         return as_requested(engine.from_tframe(out), hidden_states), engine.from_tframe(res)
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
-        return self.mixer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
+        raise NotImplementedError(NO_STEPWISE_FORM)
 
 
 class RCPSLMHead(nn.Module):

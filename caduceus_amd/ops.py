@@ -1223,3 +1223,57 @@ def proj_wgrad_only(X: torch.Tensor, Y: torch.Tensor, part: Optional[torch.Tenso
     a = L.ProjArgs(None, L.ptr(X), None, T, M, K, 0, X.stride(0), 0, None, 0, None, 0, L.ptr(Y), Y.stride(0), L.ptr(part))
     L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
     return part.sum(dim=0).t().contiguous() if own else None
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# one decode token of a left-to-right Mamba parameter set (inference only: no autograd)
+# ------------------------------------------------------------------------------------------------------------------
+def mamba_step_supported(D: int, E: int, N: int, R: int, K: int, act: torch.dtype) -> bool:
+    return bool(L.get_lib().cad_mamba_step_supported(D, E, N, R, K, L.dtype_code(act)))
+
+
+def mamba_step_scratch(B: int, E: int, N: int, R: int, device) -> torch.Tensor:
+    """The fp32 scratch buffer mamba_step needs for B rows; the caller holds it across steps (the library never allocates)."""
+    return torch.empty((int(L.get_lib().cad_mamba_step_scratch_floats(B, E, N, R)),), dtype=torch.float32, device=device)
+
+
+def mamba_step(h: torch.Tensor, conv_state: torch.Tensor, ssm_state: torch.Tensor, W_in: torch.Tensor, b_in: Optional[torch.Tensor],
+               conv_w: torch.Tensor, conv_b: Optional[torch.Tensor], W_x: torch.Tensor, W_dt: torch.Tensor, dt_bias: torch.Tensor,
+               A_log: torch.Tensor, D: torch.Tensor, W_out: torch.Tensor, b_out: Optional[torch.Tensor], scratch: torch.Tensor,
+               act: Optional[torch.dtype] = None) -> torch.Tensor:
+    """out (B, D) = one token of mamba_ssm `Mamba.step` for h (B, D) in `act` (default: h's dtype), three launches (cad_mamba_step).
+    conv_state (>= B, E, K) in `act` and ssm_state (>= B, E, N) fp32 are updated IN PLACE in their rows [0, B).  Parameters are the
+    fp32 master tensors (conv_w: (E, K) or (E, 1, K)); scratch: mamba_step_scratch(B, ...) or larger.  Inference only: nothing here is
+    recorded for autograd.  A shape the kernels do not serve raises (CAD_ERR_UNSUPPORTED); there is no other path."""
+    act = h.dtype if act is None else act
+    if h.dim() != 2 or h.dtype != act or conv_state.dtype != act or ssm_state.dtype != torch.float32:
+        raise TypeError(f"mamba_step: h (B, D) and conv_state in {act}, ssm_state in float32 "
+                        f"(got {h.dtype}, {conv_state.dtype}, {ssm_state.dtype})")
+    B, Dm = h.shape
+    E, R = W_dt.shape
+    K = conv_state.shape[2]
+    N = ssm_state.shape[2]
+    params = [W_in, b_in, conv_w, conv_b, W_x, W_dt, dt_bias, A_log, D, W_out, b_out]
+    if any(p is not None and p.dtype != torch.float32 for p in params):
+        raise TypeError("mamba_step: parameters are the fp32 master tensors")
+    params = [None if p is None else p.detach() for p in params]
+    W_in, b_in, conv_w, conv_b, W_x, W_dt, dt_bias, A_log, D, W_out, b_out = params
+    conv_w = conv_w.reshape(E, -1)
+    shapes_ok = (tuple(W_in.shape) == (2 * E, Dm) and tuple(conv_w.shape) == (E, K) and tuple(W_x.shape) == (R + 2 * N, E)
+                 and tuple(A_log.shape) == (E, N) and tuple(W_out.shape) == (Dm, E) and dt_bias.numel() == E and D.numel() == E
+                 and (b_in is None or b_in.numel() == 2 * E) and (conv_b is None or conv_b.numel() == E)
+                 and (b_out is None or b_out.numel() == Dm) and tuple(conv_state.shape[1:]) == (E, K)
+                 and tuple(ssm_state.shape[1:]) == (E, N) and conv_state.shape[0] >= B and ssm_state.shape[0] >= B and B >= 1)
+    if not shapes_ok:
+        raise ValueError("mamba_step: operand shapes do not describe one Mamba parameter set")
+    lib = L.get_lib()
+    if scratch.dtype != torch.float32 or scratch.numel() < lib.cad_mamba_step_scratch_floats(B, E, N, R):
+        raise ValueError("mamba_step: scratch must hold cad_mamba_step_scratch_floats(B, E, N, R) float32 values")
+    out = torch.empty((B, Dm), dtype=act, device=h.device)
+    stream = L.stream_and_check(h, conv_state, ssm_state, W_in, b_in, conv_w, conv_b, W_x, W_dt, dt_bias, A_log, D, W_out, b_out, scratch,
+                                out)
+    a = L.MambaStepArgs(L.ptr(h), L.ptr(out), L.ptr(conv_state), L.ptr(ssm_state), L.ptr(W_in), L.ptr(b_in), L.ptr(conv_w), L.ptr(conv_b),
+                        L.ptr(W_x), L.ptr(W_dt), L.ptr(dt_bias), L.ptr(A_log), L.ptr(D), L.ptr(W_out), L.ptr(b_out), L.ptr(scratch), B, Dm,
+                        E, N, R, K, L.dtype_code(act))
+    L.check(lib.cad_mamba_step(C.byref(a), stream), "cad_mamba_step")
+    return out

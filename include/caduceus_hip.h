@@ -567,6 +567,49 @@ int cad_proj_wxT_fp8(const cad_proj_fp8_args* a, void* stream);
 int cad_proj_fp8_supported(int K);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * One token of one left-to-right Mamba parameter set, for B independent rows.   Replaces mamba_ssm.Mamba.step
+ * (mamba_simple.py: the constant-time decode step behind `inference_params`):
+ *   xz = W_in h (+ b_in) ;  x = xz[:E], z = xz[E:]
+ *   conv_state <- shifted left by one, last column = x ;   xc = silu(b_conv + sum_k w[e,k] conv_state[e,k])
+ *   dbc = W_x xc   (R + 2N values: dt_lr, B, C) ;          delta = W_dt dbc[:R]
+ *   dt = softplus(delta + dt_bias) ;   s[e,n] <- exp(dt A[e,n]) s[e,n] + dt B[n] xc[e] ,  A = -exp(A_log)
+ *   y[e] = (sum_n C[n] s[e,n] + D[e] xc[e]) silu(z[e]) ;   out = W_out y (+ b_out)
+ * h, out: (B, D) dtype (F32, BF16 or F16).  conv_state: (>= B, E, K) dtype, ssm_state: (>= B, E, N) fp32, rows [0, B) of both
+ * UPDATED IN PLACE (rows beyond B are not touched).  Every parameter is the fp32 master tensor: W_in (2E, D), conv_w (E, K),
+ * W_x (R + 2N, E), W_dt (E, R), dt_bias / Dskip (E), A_log (E, N), W_out (D, E); b_in (2E), conv_b (E), b_out (D) or NULL.
+ * Arithmetic and accumulation are fp32; xz, xc, dbc, delta, y and out are rounded to `dtype` where the full-sequence path
+ * stores them in that dtype (a bias is rounded to `dtype` and added to the rounded product, as there), so an F32 step differs
+ * from the F32 forward by summation order only.  A row's result does not depend on the other rows or on B.
+ * scratch: cad_mamba_step_scratch_floats(B, E, N, R) floats owned by the caller.  At most three plain launches on `stream`
+ * (in_proj + conv | x_proj + dt_proj + state update + gate | out_proj), no allocation, no host synchronisation.
+ * cad_mamba_step_supported: K in [1, 4], N in [1, 64], R >= 1, D and E in [1, 2048]; anything else returns CAD_ERR_UNSUPPORTED. */
+struct cad_mamba_step_args {
+    const void* h;
+    void* out;
+    void* conv_state;
+    float* ssm_state;
+    const float* W_in;
+    const float* b_in;
+    const float* conv_w;
+    const float* conv_b;
+    const float* W_x;
+    const float* W_dt;
+    const float* dt_bias;
+    const float* A_log;
+    const float* Dskip;
+    const float* W_out;
+    const float* b_out;
+    float* scratch;
+    int64_t B;
+    int D, E, N, R, K;
+    int dtype;
+};
+typedef struct cad_mamba_step_args cad_mamba_step_args;
+int cad_mamba_step(const cad_mamba_step_args* a, void* stream);
+int cad_mamba_step_supported(int D, int E, int N, int R, int K, int dtype);
+int64_t cad_mamba_step_scratch_floats(int64_t B, int E, int N, int R);
+
+/* ---------------------------------------------------------------------------------------------------------
  * RCPS LM head + cross-entropy.   Replaces RCPSLMHead.forward (modeling_rcps.py:233-246), logits.float()
  * (modeling_caduceus.py:475) and cross_entropy(ignore_index) (modeling_caduceus.py:279-283,
  * src/tasks/metrics.py:181-184).  t-frame:  logits[b,l,v] = <W[v], t1[b,l]> + <W[comp[v]], t2[b,l]>.
