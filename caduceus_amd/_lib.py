@@ -130,6 +130,23 @@ class MambaStepArgs(C.Structure):
                 ("B", _i64), ("D", _i), ("E", _i), ("N", _i), ("R", _i), ("K", _i), ("dtype", _i)]
 
 
+class SamplerArgs(C.Structure):
+    _fields_ = [("logit_mask", _p), ("seed", C.c_uint64), ("row_offset", _i64), ("position", _i64), ("top_k", _i), ("top_p", _f),
+                ("temperature", _f)]
+
+
+class DecodeLayer(C.Structure):
+    _fields_ = [("conv_state", _p), ("ssm_state", _p), ("W_in", _p), ("b_in", _p), ("conv_w", _p), ("conv_b", _p), ("W_x", _p), ("W_dt", _p),
+                ("dt_bias", _p), ("A_log", _p), ("Dskip", _p), ("W_out", _p), ("b_out", _p), ("norm_w", _p), ("norm_b", _p),
+                ("norm_eps", _f), ("norm_is_rms", _i)]
+
+
+class DecodeArgs(C.Structure):
+    _fields_ = [("layers", C.POINTER(DecodeLayer)), ("emb", _p), ("normf_w", _p), ("normf_b", _p), ("head_w", _p), ("ids_in", _p),
+                ("logits", _p), ("ids_out", _p), ("u_out", _p), ("scratch", _p), ("sampler", SamplerArgs), ("B", _i64), ("n_layer", _i),
+                ("D", _i), ("E", _i), ("N", _i), ("R", _i), ("K", _i), ("V", _i), ("dtype", _i), ("normf_eps", _f), ("normf_is_rms", _i)]
+
+
 class LmHeadArgs(C.Structure):
     _fields_ = [("hidden", _p), ("weight", _p), ("comp", _p), ("labels", _p), ("logits", _p), ("loss_sum", _p),
                 ("count", _p), ("rows", _i64), ("D", _i), ("V", _i), ("n_strands", _i), ("ignore_index", _i64),
@@ -205,6 +222,10 @@ SYMBOLS = {
     "cad_mamba_step": (_i, [C.POINTER(MambaStepArgs), _p]),
     "cad_mamba_step_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "cad_mamba_step_scratch_floats": (_i64, [_i64, _i, _i, _i]),
+    "cad_sample_tokens": (_i, [_p, _i64, _i, C.POINTER(SamplerArgs), _p, _p, _p]),
+    "cad_decode_token": (_i, [C.POINTER(DecodeArgs), _p]),
+    "cad_decode_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "cad_decode_scratch_floats": (_i64, [_i64, _i, _i]),
     "cad_lm_head_fwd": (_i, [C.POINTER(LmHeadArgs), _p]),
     "cad_lm_head_partials": (_i64, [_i64]),
     "cad_lm_head_bwd": (_i, [C.POINTER(LmHeadBwdArgs), _p]),

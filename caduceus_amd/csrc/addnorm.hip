@@ -3,8 +3,13 @@
 //
 // One wave64 per token row; lane handles channels c = lane + 64*k.  HBM-bound elementwise kernel: every input
 // byte is read once and every output byte written once; statistics stay in registers (wave xor-reduction).
+//
+// cad_rownorm.h holds the wave reduction used here (cad_row_wave_sum) and MIRRORS the forward kernels' per-lane walk for a row held in
+// LDS (decode.hip): a change to the order in which add_norm_fwd_kernel / add_norm_fwd_vec_kernel sum a row, or to where they round,
+// is a change to make there too.
 #include "cad_common.h"
 #include "cad_fp8.h"
+#include "cad_rownorm.h"
 #include "cad_stream.h"
 
 namespace {
@@ -12,11 +17,7 @@ namespace {
 #define AN_KMAX 16  // D <= 64 * AN_KMAX = 1024
 #define AN_WAVES 4  // rows per block-iteration
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
+__device__ __forceinline__ float wave_sum(float v) { return cad_row_wave_sum(v); }  // (one butterfly for both files)
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));

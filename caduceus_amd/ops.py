@@ -1277,3 +1277,103 @@ def mamba_step(h: torch.Tensor, conv_state: torch.Tensor, ssm_state: torch.Tenso
                         E, N, R, K, L.dtype_code(act))
     L.check(lib.cad_mamba_step(C.byref(a), stream), "cad_mamba_step")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# token sampler and the whole decode token of a causal stack (cad_sample_tokens / cad_decode_token)
+# ------------------------------------------------------------------------------------------------------------------
+SAMPLER_VMAX = 64
+
+
+def philox_uniform(seed: int, r: int, position: int) -> float:
+    """The uniform in [0, 1) the kernels draw for (seed, r = row_offset + row, position): the first word of Philox4x32-10 with key
+    (seed low, seed high) and counter (r low, r high, position low, position high), its top 24 bits.  Plain integers on the host."""
+    m32 = 0xFFFFFFFF
+    c = [r & m32, (r >> 32) & m32, position & m32, (position >> 32) & m32]
+    k0, k1 = seed & m32, (seed >> 32) & m32
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & m32, (p0 >> 32) ^ c[3] ^ k1, p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & m32, (k1 + 0xBB67AE85) & m32
+    return (c[0] >> 8) * 2.0 ** -24
+
+
+def check_sampling(top_k: int, top_p: float, temperature: float):
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be a non-negative integer (0 keeps every token), got {top_k}")
+    if not 0.0 <= top_p <= 1.0:
+        raise ValueError(f"top_p must lie in [0, 1], got {top_p}")
+    if not temperature > 0.0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+
+
+def sampler_args(top_k=1, top_p=0.0, temperature=1.0, seed=0, row_offset=0, position=0, logit_mask=None) -> L.SamplerArgs:
+    check_sampling(top_k, top_p, temperature)
+    return L.SamplerArgs(L.ptr(logit_mask), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), int(position), int(top_k), float(top_p),
+                         float(temperature))
+
+
+def _sample_tokens_torch(x, top_k, top_p, temperature, u):
+    """cad_sample_tokens' rules (include/caduceus_hip.h) in torch ops, for vocabularies beyond the kernel's 64 ids."""
+    B, V = x.shape
+    ar = torch.arange(V, device=x.device).expand(B, V)
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices  # ties: the lower id first
+    rank = torch.empty_like(order).scatter_(1, order, ar)
+    if top_k == 1:
+        return order[:, 0]
+    keep_n = V if top_k == 0 or top_k > V else top_k
+    keep = rank < keep_n
+    if temperature != 1.0:
+        x = x / temperature
+    mx = torch.where(keep, x, torch.full_like(x, float("-inf"))).amax(-1, keepdim=True)
+    e = torch.where(keep, torch.exp(x - mx), torch.zeros_like(x)).nan_to_num(nan=0.0)
+    if 0.0 < top_p < 1.0:
+        p_sorted = (e / e.sum(-1, keepdim=True)).gather(1, order)
+        cum = p_sorted.flip(-1).cumsum(-1).flip(-1).gather(1, rank)  # this entry and everything ranked behind it
+        drop = keep & (rank != 0) & (cum <= 1.0 - top_p)
+        keep, e = keep & ~drop, torch.where(drop, torch.zeros_like(e), e)
+    cdf = e.cumsum(-1)
+    live = keep & (e > 0)
+    first = torch.where(live & (cdf > u[:, None] * cdf[:, -1:]), ar, torch.full_like(ar, V)).amin(-1)
+    last = torch.where(live, ar, torch.full_like(ar, -1)).amax(-1)
+    return torch.where(first < V, first, torch.where(last >= 0, last, order[:, 0]))
+
+
+def sample_tokens(logits: torch.Tensor, top_k: int = 1, top_p: float = 0.0, temperature: float = 1.0, seed: int = 0, row_offset: int = 0,
+                  position: int = 0, logit_mask: Optional[torch.Tensor] = None, return_u: bool = False):
+    """ids (B) int64 sampled from logits (B, V) fp32 by the rules of cad_sample_tokens (mamba_ssm's `sample`: logit_mask (V) of 0 / -inf,
+    top_k, temperature, top_p, inverse CDF at the uniform keyed by (seed, row_offset + row, position)).  V <= 64 runs the kernel, one
+    launch; a larger vocabulary the same rules in torch ops.  return_u: also the uniforms (B) fp32 the rows consumed."""
+    check_sampling(top_k, top_p, temperature)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise TypeError("sample_tokens: logits (B, V) float32")
+    B, V = logits.shape
+    if logit_mask is not None and (logit_mask.dtype != torch.float32 or logit_mask.numel() != V):
+        raise TypeError("sample_tokens: logit_mask holds V float32 values (0 or -inf)")
+    logits = logits.contiguous()
+    if V > SAMPLER_VMAX:
+        u = torch.tensor([philox_uniform(int(seed) & 0xFFFFFFFFFFFFFFFF, row_offset + b, position) for b in range(B)], dtype=torch.float32,
+                         device=logits.device)
+        ids = _sample_tokens_torch(logits if logit_mask is None else logits + logit_mask, int(top_k), float(top_p), float(temperature), u)
+        return (ids, u) if return_u else ids
+    ids = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    u = torch.empty((B,), dtype=torch.float32, device=logits.device) if return_u else None
+    stream = L.stream_and_check(logits, logit_mask, ids, u)
+    s = sampler_args(top_k, top_p, temperature, seed, row_offset, position, logit_mask)
+    L.check(L.get_lib().cad_sample_tokens(L.ptr(logits), B, V, C.byref(s), L.ptr(ids), L.ptr(u), stream), "cad_sample_tokens")
+    return (ids, u) if return_u else ids
+
+
+def decode_supported(D: int, E: int, N: int, R: int, K: int, V: int, act: torch.dtype) -> bool:
+    return bool(L.get_lib().cad_decode_supported(D, E, N, R, K, V, L.dtype_code(act)))
+
+
+def decode_scratch(B: int, D: int, E: int, device) -> torch.Tensor:
+    """The fp32 scratch of decode_token for B rows; the caller holds it across tokens (the library never allocates)."""
+    return torch.empty((int(L.get_lib().cad_decode_scratch_floats(B, D, E)),), dtype=torch.float32, device=device)
+
+
+def decode_token(args: "L.DecodeArgs", stream) -> None:
+    """One generated token of a causal stack: cad_decode_token on a prepared argument record (generation.DecodeStack builds it once and
+    keeps every tensor it points to alive).  3 n_layer + 1 launches on `stream`, nothing allocated, nothing read back."""
+    L.check(L.get_lib().cad_decode_token(C.byref(args), stream), "cad_decode_token")

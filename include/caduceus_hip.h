@@ -610,6 +610,91 @@ int cad_mamba_step_supported(int D, int E, int N, int R, int K, int dtype);
 int64_t cad_mamba_step_scratch_floats(int64_t B, int E, int N, int R);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Token sampler and the whole decode token of a causal stack in one call.   Replaces the per-token python loop of
+ * mamba_ssm.utils.generation (decode + sample with top_k / top_p / temperature).
+ *
+ * Sampler, for one row of V <= 64 fp32 logits (id = position in the row):
+ *   1. logit_mask (V floats, 0 or -inf; NULL = none) is added.
+ *   2. top_k == 1: the argmax, ties to the lowest id.  Nothing below applies.
+ *   3. top_k > 1: the min(top_k, V) largest logits are kept, ties at the cut to the lower id; top_k == 0 keeps all.
+ *   4. kept logits are divided by temperature when it is not 1.
+ *   5. 0 < top_p < 1: with p = softmax over the kept entries, ordered ascending by p (among equal p the higher id first), an entry
+ *      whose ascending cumulative probability is <= 1 - top_p is removed; the most probable entry (lowest id among equals) survives.
+ *   6. softmax over the survivors in fp32; the CDF accumulated in id order is inverted at u: the first id whose cumulative weight
+ *      exceeds u * total (the last survivor of non-zero weight if rounding leaves none).
+ * u = (x >> 8) * 2^-24 in [0, 1), x the first output word of Philox4x32-10 with key (seed low, seed high) and counter
+ * (r low, r high, position low, position high), r = row_offset + row.  No state in memory: the same (seed, r, position) gives the
+ * same u, whatever the batch or the call. */
+struct cad_sampler_args {
+    const float* logit_mask;
+    uint64_t seed;
+    int64_t row_offset;
+    int64_t position;
+    int top_k;
+    float top_p;
+    float temperature;
+};
+typedef struct cad_sampler_args cad_sampler_args;
+/* ids_out (B) int64 <- one id per row of logits (B, V) fp32; u_out (B) fp32 or NULL: the uniform each row consumed.  One launch, one wave
+ * per row.  V > 64 returns CAD_ERR_UNSUPPORTED; top_k < 0, top_p outside [0, 1] or temperature <= 0 CAD_ERR_BAD_ARG. */
+int cad_sample_tokens(const float* logits, int64_t B, int V, const cad_sampler_args* s, int64_t* ids_out, float* u_out, void* stream);
+
+/* One layer of cad_decode_token: the parameter and state pointers of cad_mamba_step_args plus the block's norm. */
+struct cad_decode_layer {
+    void* conv_state;
+    float* ssm_state;
+    const float* W_in;
+    const float* b_in;
+    const float* conv_w;
+    const float* conv_b;
+    const float* W_x;
+    const float* W_dt;
+    const float* dt_bias;
+    const float* A_log;
+    const float* Dskip;
+    const float* W_out;
+    const float* b_out;
+    const float* norm_w;
+    const float* norm_b;
+    float norm_eps;
+    int norm_is_rms;
+};
+typedef struct cad_decode_layer cad_decode_layer;
+/* One generated token of a causal stack (embedding, n_layer x [add + norm, Mamba step], final add + norm, bias-free LM head, sampler)
+ * for B rows: 3 n_layer + 1 plain launches on `stream`, no allocation, no synchronisation, kernel boundaries as the only grid-wide
+ * ordering.  Launch 1 of a layer forms residual' = hidden + residual (fp32, written once per row), normalises it in the summation
+ * order of cad_add_norm_fwd, rounds to `dtype` and continues as cad_mamba_step's launch 1; launches 2 and 3 are cad_mamba_step's.
+ * The last launch does the final add + norm, logits = W_head hn and the sampler, one wave per row.
+ * layers: HOST array of n_layer records (read during the call only).  emb: (V, D) fp32; ids_in (B) int64, an id outside [0, V) is
+ * clamped into it.  head_w: (V, D) fp32.  logits (B, V) fp32 always written; ids_out (B) int64; u_out (B) fp32 or NULL.  ids_out may
+ * be ids_in.  conv_state / ssm_state rows [0, B) are updated in place.  scratch: cad_decode_scratch_floats(B, D, E) floats.
+ * cad_decode_supported: what cad_mamba_step_supported serves, with 1 <= V <= 64; anything else returns CAD_ERR_UNSUPPORTED before
+ * anything is launched. */
+struct cad_decode_args {
+    const cad_decode_layer* layers;
+    const float* emb;
+    const float* normf_w;
+    const float* normf_b;
+    const float* head_w;
+    const int64_t* ids_in;
+    float* logits;
+    int64_t* ids_out;
+    float* u_out;
+    float* scratch;
+    cad_sampler_args sampler;
+    int64_t B;
+    int n_layer;
+    int D, E, N, R, K, V;
+    int dtype;
+    float normf_eps;
+    int normf_is_rms;
+};
+typedef struct cad_decode_args cad_decode_args;
+int cad_decode_token(const cad_decode_args* a, void* stream);
+int cad_decode_supported(int D, int E, int N, int R, int K, int V, int dtype);
+int64_t cad_decode_scratch_floats(int64_t B, int D, int E);
+
+/* ---------------------------------------------------------------------------------------------------------
  * RCPS LM head + cross-entropy.   Replaces RCPSLMHead.forward (modeling_rcps.py:233-246), logits.float()
  * (modeling_caduceus.py:475) and cross_entropy(ignore_index) (modeling_caduceus.py:279-283,
  * src/tasks/metrics.py:181-184).  t-frame:  logits[b,l,v] = <W[v], t1[b,l]> + <W[comp[v]], t2[b,l]>.
