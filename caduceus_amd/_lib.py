@@ -159,6 +159,12 @@ class LmHeadBwdArgs(C.Structure):
                 ("n_strands", _i), ("ignore_index", _i64), ("dtype", _i), ("ld", _i64)]
 
 
+class LmScoreArgs(C.Structure):
+    _fields_ = [("hidden", _p), ("weight", _p), ("comp", _p), ("row_index", _p), ("targets", _p), ("logit_mask", _p), ("logp", _p),
+                ("logp_all", _p), ("rows", _i64), ("n", _i64), ("D", _i), ("V", _i), ("n_strands", _i), ("ignore_index", _i64),
+                ("dtype", _i)]
+
+
 # every exported symbol of include/caduceus_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "cad_version": (C.c_char_p, []),
@@ -231,6 +237,8 @@ SYMBOLS = {
     "cad_lm_head_bwd": (_i, [C.POINTER(LmHeadBwdArgs), _p]),
     "cad_lm_head_bwd_supported": (_i, [_i, _i]),
     "cad_lm_head_bwd_partials": (_i64, [_i64]),
+    "cad_lm_head_score": (_i, [C.POINTER(LmScoreArgs), _p]),
+    "cad_lm_head_score_supported": (_i, [_i, _i, _i]),
     "cad_tokenize_mlm": (_i, [C.POINTER(MlmArgs), _p]),
     "cad_mlm_threshold": (C.c_uint32, [C.c_double]),
     "cad_hg38_interval": (_i, [_i64, _i64, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),

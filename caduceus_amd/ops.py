@@ -8,6 +8,7 @@ memory, streams and the autograd graph; all arithmetic of these ops happens in t
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -696,6 +697,77 @@ def lm_head(hidden: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Ten
     own_b16: the backward's torch-op branch (shapes cad_lm_head_bwd does not take) multiplies bf16 on cad_gemm_b16, not the library."""
     logits, loss = _LmHead.apply(hidden, weight, comp, labels, ignore_index, own_b16)
     return logits, (loss if labels is not None else None)
+
+
+class ScoreUnsupported(ValueError):
+    """The head lies outside what cad_lm_head_score serves (a bias-free head with vocab_size <= 16 on fp32 / bf16 / fp16 hidden)."""
+
+
+def lm_head_score_supported(D: int, V: int, act: torch.dtype) -> bool:
+    if act not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    return bool(L.get_lib().cad_lm_head_score_supported(int(D), int(V), L.dtype_code(act)))
+
+
+def lm_head_score(hidden_t: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor], targets: Optional[torch.Tensor] = None,
+                  row_index: Optional[torch.Tensor] = None, logit_mask: Optional[torch.Tensor] = None, want_all: bool = False,
+                  ignore_index: int = -100):
+    """Log-probabilities from the final t-frame hidden state (S, ..., D) in one launch (cad_lm_head_score); no logits tensor exists.
+    row_index: int64 rows of the flattened (rows, D) hidden to score (any shape, any order, repeats allowed); None scores every row.
+    targets: int64, one per scored row -> logp = log softmax(z + logit_mask)[target], 0.0 where the target is ignore_index or outside
+    [0, V), -inf where it is masked.  want_all -> logp_all (..., V).  logit_mask: (V) fp32 of 0 / -inf (generation._logit_mask).
+    Returns logp, logp_all, or (logp, logp_all) when both are asked for, shaped like row_index (or like hidden's row dimensions).
+    No autograd: tensors that require grad are refused while grad mode is on.  A head the kernel does not serve raises ScoreUnsupported."""
+    if targets is None and not want_all:
+        raise ValueError("lm_head_score: give targets, want_all=True, or both")
+    if torch.is_grad_enabled() and (hidden_t.requires_grad or weight.requires_grad):
+        raise RuntimeError("lm_head_score has no backward: call it under torch.no_grad() (or detach its inputs); the differentiable head "
+                           "is ops.lm_head")
+    S, D = hidden_t.shape[0], hidden_t.shape[-1]
+    V = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != D:
+        raise ValueError(f"lm_head_score: weight must be (V, {D}), got {tuple(weight.shape)}")
+    if not lm_head_score_supported(D, V, hidden_t.dtype):
+        raise ScoreUnsupported(f"lm_head_score: cad_lm_head_score does not serve d_model {D}, vocab_size {V} in {hidden_t.dtype} "
+                               "(vocab_size <= 16; float32, bfloat16 or float16 hidden); score such a head from model(ids).logits")
+    if S not in (1, 2) or (S == 2 and comp is None):
+        raise ValueError("lm_head_score: hidden is (1, ..., D), or (2, ..., D) with a complement map")
+    hidden = hidden_t.detach().contiguous()
+    rows = hidden.numel() // (S * D)
+    w = weight.detach().float().contiguous()
+    dev = hidden.device
+    if row_index is not None:
+        if row_index.dtype != torch.int64:
+            raise TypeError("lm_head_score: row_index is int64")
+        if row_index.device.type == "cpu" and row_index.numel() and (int(row_index.min()) < 0 or int(row_index.max()) >= rows):
+            raise ValueError(f"lm_head_score: row_index must lie in [0, {rows})")
+        shape = tuple(row_index.shape)
+        ridx = row_index.reshape(-1).contiguous()
+    else:
+        shape, ridx = tuple(hidden.shape[1:-1]), None
+    n = math.prod(shape)
+    if n == 0 or rows == 0:
+        raise ValueError("lm_head_score: nothing to score")
+    tg = None
+    if targets is not None:
+        if targets.numel() != n:
+            raise ValueError(f"lm_head_score: {n} rows are scored, targets holds {targets.numel()}")
+        tg = targets.reshape(-1).long().contiguous()
+    if logit_mask is not None:
+        if logit_mask.dtype != torch.float32 or logit_mask.numel() != V:
+            raise TypeError("lm_head_score: logit_mask holds V float32 values (0 or -inf)")
+        logit_mask = logit_mask.contiguous()
+        if logit_mask.device.type == "cpu" and not bool((logit_mask == 0).any()):
+            raise ValueError("lm_head_score: logit_mask allows no id")
+    logp = torch.empty(shape, dtype=torch.float32, device=dev) if tg is not None else None
+    logp_all = torch.empty(shape + (V,), dtype=torch.float32, device=dev) if want_all else None
+    stream = L.stream_and_check(hidden, w, comp if S == 2 else None, ridx, tg, logit_mask, logp, logp_all)
+    a = L.LmScoreArgs(L.ptr(hidden), L.ptr(w), L.ptr(comp) if S == 2 else None, L.ptr(ridx), L.ptr(tg), L.ptr(logit_mask), L.ptr(logp),
+                      L.ptr(logp_all), rows, n, D, V, S, int(ignore_index), L.dtype_code(hidden.dtype))
+    L.check(L.get_lib().cad_lm_head_score(C.byref(a), stream), "cad_lm_head_score")
+    if logp is None:
+        return logp_all
+    return (logp, logp_all) if want_all else logp
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -751,6 +751,39 @@ int cad_lm_head_bwd(const cad_lm_head_bwd_args* a, void* stream);
 int cad_lm_head_bwd_supported(int D, int V);
 int64_t cad_lm_head_bwd_partials(int64_t rows);
 
+/* Score head: per-token log-probabilities straight from the final hidden state, in one launch; the logits are never written.
+ *   z[i]        = the logit row cad_lm_head_fwd forms for row r_i of hidden (fp32 accumulation, each strand's sum kept apart, then one
+ *                 commutative add), r_i = row_index[i], or i where row_index is NULL
+ *   logp_all[i] = log softmax(z[i] + logit_mask): the log-sum-exp runs over the allowed ids only, a masked id gives -inf
+ *   logp[i]     = logp_all[i][targets[i]]; a target equal to ignore_index or outside [0, V) gives 0.0f (the forward skips such labels,
+ *                 so a sum over a row stays the sum over its counted tokens); a masked target gives -inf
+ * hidden: (S, rows, D) F32 / BF16 / F16.  weight: (V, D) fp32.  comp: S == 2 only.  row_index: (n) int64 rows of hidden in any order,
+ * repeats allowed, or NULL (then n <= rows); an index outside [0, rows) reads nothing and gives NaN.  targets: (n) int64, needed with
+ * logp.  logit_mask: (V) fp32, 0 at allowed ids and -inf elsewhere (the sampler's mask), or NULL; it must allow at least one id --
+ * the caller that builds it knows (the library cannot see it without reading device memory back; a mask of -inf alone gives NaN).
+ * logp (n) and logp_all (n, V) fp32: at least one is given, the other may be NULL.
+ * One launch on `stream`, no allocation, no synchronisation, no atomics: every output element has one writer, and a row's result does
+ * not depend on which other rows are scored with it.  cad_lm_head_score_supported: any D >= 1, 1 <= V <= 16, the three dtypes; anything
+ * else returns CAD_ERR_UNSUPPORTED.  D 128 / 256 (512 in bf16) with a 16-byte aligned hidden run on the matrix cores
+ * (v_mfma_f32_16x16x4_f32 on tiles of 16 scored rows, gathered through row_index), everything else one wave per scored row. */
+struct cad_lm_score_args {
+    const void* hidden;
+    const float* weight;
+    const int64_t* comp;
+    const int64_t* row_index;
+    const int64_t* targets;
+    const float* logit_mask;
+    float* logp;
+    float* logp_all;
+    int64_t rows, n;
+    int D, V, n_strands;
+    int64_t ignore_index;
+    int dtype;
+};
+typedef struct cad_lm_score_args cad_lm_score_args;
+int cad_lm_head_score(const cad_lm_score_args* a, void* stream);
+int cad_lm_head_score_supported(int D, int V, int dtype);
+
 /* ---------------------------------------------------------------------------------------------------------
  * hg38 data path -- the step in front of the model.
  *
