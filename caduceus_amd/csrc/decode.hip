@@ -5,12 +5,12 @@
 //                              Every workgroup normalises the <= ST_BT rows it stages (redundant, D values per row against the 2 D
 //                              weights per channel it reads anyway); the workgroups of column 0 write residual'.
 //   2., 3.                     step_ssm_kernel, step_out_kernel: unchanged.
-// and one tail launch, one wave per row: final add + norm, logits = W_head hn (lm_head_fwd_kernel's lane-strided order), sampler.
+// and one tail launch, one wave per row: final add + norm, logits = W_head hn (cad_head.h's scalar row), sampler.
 // residual' goes to the other of two buffers (a workgroup of another column may still be reading the residual), so the kernel
 // boundaries stay the only grid-wide ordering: 3 n_layer + 1 plain launches, no allocation, no synchronisation.
 #include <math.h>
 
-#include "cad_rownorm.h"
+#include "cad_head.h"
 #include "step_kernels.h"
 
 namespace {
@@ -188,23 +188,9 @@ __global__ __launch_bounds__(64 * DC_WAVES) void decode_tail_kernel(dc_tail a, c
     }
     __syncthreads();  // the head walks the row with another lane map
     if (!live) return;
-    float acc[VMAX];
-#pragma unroll
-    for (int v = 0; v < VMAX; ++v) acc[v] = 0.f;
-    for (int c = lane; c < D; c += 64) {
-        const float hv = row[c];
-#pragma unroll
-        for (int v = 0; v < VMAX; ++v)
-            if (v < V) acc[v] += hv * a.head_w[(int64_t)v * D + c];
-    }
-    float mine = 0.f;  // lane v keeps logit v
-#pragma unroll
-    for (int v = 0; v < VMAX; ++v) {
-        if (v < V) {  // wave-uniform
-            const float t = cad_row_wave_sum(acc[v]);
-            if (lane == v) mine = t;
-        }
-    }
+    float z[VMAX];
+    cad_head_row(z, (const float*)row, (const float*)nullptr, a.head_w, nullptr, D, V, lane);
+    const float mine = cad_head_row_at(z, lane);  // lane v keeps logit v
     if (lane < V) a.logits[r * V + lane] = mine;
     float x = mine;
     if (s.logit_mask && lane < V) x += s.logit_mask[lane];

@@ -344,3 +344,23 @@ def test_score_struct_matches_the_compiler(tmp_path):
     got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
     assert got[0] == C.sizeof(L.LmScoreArgs)
     assert got[1:] == [getattr(L.LmScoreArgs, f).offset for f in fields]
+
+
+@pytest.mark.parametrize("D,dtype,S", [(128, BF, 2), (256, HF, 1), (512, BF, 2), (40, F32, 2)],
+                         ids=["D128-bf16-S2", "D256-f16-S1", "D512-bf16-S2", "D40-f32-S2"])
+def test_score_is_the_negated_single_row_loss(backend, D, dtype, S):
+    """The promise csrc/cad_head.h exists for: a sequence log-likelihood equals what the training loss saw.  One score call over 19 rows
+    against 19 forward calls on the single-row slices with the row's target as the label: the loss of one counted row is
+    (lse - z[t]) / 1, the exact negation of logp = z[t] - lse, so the two agree bit for bit (three matrix-core widths, and the one-wave-
+    per-row path at D = 40)."""
+    name, dev = backend
+    R, V = 19, 16
+    h, W, _, _ = lm_inputs(S, R, D, V, dtype, 800 + D)
+    t = torch.randint(0, V, (R,), generator=torch.Generator().manual_seed(D + S))
+    comp = COMP if S == 2 else None
+    logp = run_score(dev, h, W, comp, t, want_all=False, ign=-100).cpu()
+    hd, wd, cd, td = h.to(dev), W.to(dev), None if comp is None else comp.to(dev), t.to(dev)
+    with torch.no_grad():
+        loss = torch.stack([ops.lm_head(hd[:, r:r + 1].reshape(S, 1, 1, D), wd, cd, td[r:r + 1].reshape(1, 1), -100)[1] for r in range(R)]).cpu()
+    print(f"[bits] {name} D{D} S{S}: max |logp + loss| = {float((logp.double() + loss.double()).abs().max()):.3e}")
+    assert bool(torch.isfinite(logp).all()) and torch.equal(logp, -loss)
