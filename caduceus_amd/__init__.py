@@ -13,11 +13,12 @@ from .downstream import DNAEmbeddingModelCaduceus, SequenceDecoder
 from .mamba import fp16_kernels
 from .generation import InferenceParams, decode_step, generate
 from .scoring import masked_logprobs, sequence_logprobs, variant_llr
+from .infilling import infill
 
 __all__ = ["DNAEmbeddingModelCaduceus", "SequenceDecoder", "CaduceusConfig", "Caduceus", "CaduceusForMaskedLM", "CaduceusForSequenceClassification",
            "CaduceusTokenizer", "CaduceusMixerModel", "BiMambaWrapper", "create_block", "RCPSEmbedding", "RCPSWrapper",
            "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "fp16_kernels", "register_auto_classes", "InferenceParams",
-           "decode_step", "generate", "sequence_logprobs", "masked_logprobs", "variant_llr"]
+           "decode_step", "generate", "sequence_logprobs", "masked_logprobs", "variant_llr", "infill"]
 
 
 def register_auto_classes():

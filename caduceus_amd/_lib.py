@@ -165,6 +165,12 @@ class LmScoreArgs(C.Structure):
                 ("dtype", _i)]
 
 
+class LmUnmaskArgs(C.Structure):
+    _fields_ = [("hidden", _p), ("weight", _p), ("comp", _p), ("ids_in", _p), ("ids_out", _p), ("conf", _p), ("u_out", _p),
+                ("sampler", SamplerArgs), ("rows", _i64), ("L", _i64), ("D", _i), ("V", _i), ("n_strands", _i), ("mask_id", _i64),
+                ("dtype", _i)]
+
+
 # every exported symbol of include/caduceus_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "cad_version": (C.c_char_p, []),
@@ -239,6 +245,8 @@ SYMBOLS = {
     "cad_lm_head_bwd_partials": (_i64, [_i64]),
     "cad_lm_head_score": (_i, [C.POINTER(LmScoreArgs), _p]),
     "cad_lm_head_score_supported": (_i, [_i, _i, _i]),
+    "cad_lm_head_unmask": (_i, [C.POINTER(LmUnmaskArgs), _p]),
+    "cad_lm_head_unmask_supported": (_i, [_i, _i, _i]),
     "cad_tokenize_mlm": (_i, [C.POINTER(MlmArgs), _p]),
     "cad_mlm_threshold": (C.c_uint32, [C.c_double]),
     "cad_hg38_interval": (_i, [_i64, _i64, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -1,5 +1,5 @@
-// The LM head's logit row, stated once for the kernels that form it: cad_lm_head_fwd (lmhead.hip), cad_lm_head_score (score.hip) and the
-// tail of cad_decode_token (decode.hip).
+// The LM head's logit row, stated once for the kernels that form it: cad_lm_head_fwd (lmhead.hip), cad_lm_head_score (score.hip), the
+// tail of cad_decode_token (decode.hip) and cad_lm_head_unmask (unmask.hip).
 //   z[v] = <h0, W[v]> + <h1, W[comp v]>     fp32 accumulation, each strand's sum kept apart, then ONE commutative add per logit: logits(x)[v]
 //                                           and logits(RC x)[comp v] (strand roles exchanged) are the same two numbers added, bit for bit,
 //                                           like the reference's `fwd_logits + rc_logits` (modeling_rcps.py:240-246)
@@ -73,9 +73,12 @@ __device__ __forceinline__ float cad_head_row_at(const float (&z)[VMAX], int64_t
 // row_of(tile) names the row of `hid` (rows x D per strand) that this lane loads for the tile, i.e. the tile's row jl; a tail tile
 // names valid rows that the caller never stores.  epilogue(tile, z): lane (column jl, rows 4 g + r) holds logit jl of the tile's rows
 // 4 g + r in z[r].  The next tile's strand 0 is in flight under strand 1's MFMAs, its strand 1 under the epilogue.
-template <typename T, int NJ, typename RowOf, typename Epilogue>
-__device__ __forceinline__ void cad_head_mfma_walk(const T* hid, int64_t rows, const float* weight, const int64_t* comp, int n_strands, int V,
-                                                   int64_t tile, int64_t tstep, int64_t ntiles, int lane, RowOf row_of, Epilogue epilogue) {
+// take(tile): wave-uniform; a tile it declines is neither loaded nor multiplied nor handed to the epilogue (whatever such a tile owes its
+// outputs is take's own to write), and the prefetch goes to the next tile of the walk that is taken.
+template <typename T, int NJ, typename Take, typename RowOf, typename Epilogue>
+__device__ __forceinline__ void cad_head_mfma_walk_if(const T* hid, int64_t rows, const float* weight, const int64_t* comp, int n_strands, int V,
+                                                      int64_t tile, int64_t tstep, int64_t ntiles, int lane, Take take, RowOf row_of,
+                                                      Epilogue epilogue) {
     const int g = lane >> 4, jl = lane & 15;
     constexpr int D = 32 * NJ;
     constexpr int WPT = sizeof(T) * 8 / 4;  // 32-bit words per 8 elements
@@ -112,15 +115,21 @@ __device__ __forceinline__ void cad_head_mfma_walk(const T* hid, int64_t rows, c
         }
         return z;
     };
+    auto next_taken = [&](int64_t t) {
+        while (t < ntiles && !take(t)) t += tstep;
+        return t;
+    };
     Raw h0[NJ], h1[NJ];
+    tile = next_taken(tile);
     if (tile < ntiles) {
         const int64_t row = row_of(tile);
         load_tile(row, 0, h0);
         if (n_strands == 2) load_tile(row, 1, h1);
     }
-    for (; tile < ntiles; tile += tstep) {
-        const bool more = tile + tstep < ntiles;
-        const int64_t nrow = more ? row_of(tile + tstep) : 0;
+    for (int64_t next; tile < ntiles; tile = next) {
+        next = next_taken(tile + tstep);
+        const bool more = next < ntiles;
+        const int64_t nrow = more ? row_of(next) : 0;
         f32x4 z0 = product(h0);
         if (more) load_tile(nrow, 0, h0);
         if (n_strands == 2) {
@@ -131,6 +140,13 @@ __device__ __forceinline__ void cad_head_mfma_walk(const T* hid, int64_t rows, c
         }
         epilogue(tile, z0);
     }
+}
+// every tile of the walk (tile, tile + tstep, .. < ntiles)
+template <typename T, int NJ, typename RowOf, typename Epilogue>
+__device__ __forceinline__ void cad_head_mfma_walk(const T* hid, int64_t rows, const float* weight, const int64_t* comp, int n_strands, int V,
+                                                   int64_t tile, int64_t tstep, int64_t ntiles, int lane, RowOf row_of, Epilogue epilogue) {
+    cad_head_mfma_walk_if<T, NJ>(hid, rows, weight, comp, n_strands, V, tile, tstep, ntiles, lane, [](int64_t) { return true; }, row_of,
+                                 epilogue);
 }
 
 // reductions over the 16 lanes that hold one row of a tile (xor butterfly 8 .. 1; every lane of the row receives the result)

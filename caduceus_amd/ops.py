@@ -770,6 +770,61 @@ def lm_head_score(hidden_t: torch.Tensor, weight: torch.Tensor, comp: Optional[t
     return (logp, logp_all) if want_all else logp
 
 
+def lm_head_unmask_supported(D: int, V: int, act: torch.dtype) -> bool:
+    if act not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    return bool(L.get_lib().cad_lm_head_unmask_supported(int(D), int(V), L.dtype_code(act)))
+
+
+def lm_head_unmask(hidden_t: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor], ids: torch.Tensor, *, mask_token_id: int,
+                   top_k: int = 1, top_p: float = 0.0, temperature: float = 1.0, seed: int = 0, row_offset: int = 0, position: int = 0,
+                   logit_mask: Optional[torch.Tensor] = None, return_u: bool = False):
+    """One round of iterative unmasking from the final t-frame hidden state (S, B, L, D) in one launch (cad_lm_head_unmask); neither
+    logits nor log-probabilities per id exist.  ids (B, L) int64: where it equals mask_token_id the position is open and gets the id the
+    sampler draws from its logit row (sample_tokens' rules; the uniform keyed by (seed, row_offset + b, position + l)) and, as conf, the
+    model's own log-probability of that id over the ids logit_mask allows (lm_head_score's number: temperature, top_k and top_p not
+    applied); every other position keeps its id and gets conf 0.0.  Returns (ids_out (B, L) int64, conf (B, L) fp32[, u (B, L) fp32]);
+    ids is left as it is.  No autograd, as lm_head_score.  A head the kernel does not serve raises ScoreUnsupported."""
+    check_sampling(top_k, top_p, temperature)
+    if torch.is_grad_enabled() and (hidden_t.requires_grad or weight.requires_grad):
+        raise RuntimeError("lm_head_unmask has no backward: call it under torch.no_grad() (or detach its inputs)")
+    if hidden_t.dim() != 4:
+        raise ValueError(f"lm_head_unmask: hidden is (S, B, L, D), got {tuple(hidden_t.shape)}")
+    S, B, Lq, D = hidden_t.shape
+    V = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != D:
+        raise ValueError(f"lm_head_unmask: weight must be (V, {D}), got {tuple(weight.shape)}")
+    if not lm_head_unmask_supported(D, V, hidden_t.dtype):
+        raise ScoreUnsupported(f"lm_head_unmask: cad_lm_head_unmask does not serve d_model {D}, vocab_size {V} in {hidden_t.dtype} "
+                               "(vocab_size <= 16; float32, bfloat16 or float16 hidden)")
+    if S not in (1, 2) or (S == 2 and comp is None):
+        raise ValueError("lm_head_unmask: hidden is (1, B, L, D), or (2, B, L, D) with a complement map")
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (B, Lq):
+        raise TypeError(f"lm_head_unmask: ids is ({B}, {Lq}) int64")
+    if B * Lq == 0:
+        raise ValueError("lm_head_unmask: nothing to unmask")
+    if logit_mask is not None:
+        if logit_mask.dtype != torch.float32 or logit_mask.numel() != V:
+            raise TypeError("lm_head_unmask: logit_mask holds V float32 values (0 or -inf)")
+        logit_mask = logit_mask.contiguous()
+        if logit_mask.device.type == "cpu" and not bool((logit_mask == 0).any()):
+            raise ValueError("lm_head_unmask: logit_mask allows no id")
+    hidden = hidden_t.detach().contiguous()
+    w = weight.detach().float().contiguous()
+    ids = ids.contiguous()
+    dev = hidden.device
+    ids_out = torch.empty((B, Lq), dtype=torch.int64, device=dev)
+    conf = torch.empty((B, Lq), dtype=torch.float32, device=dev)
+    u = torch.empty((B, Lq), dtype=torch.float32, device=dev) if return_u else None
+    cmap = comp if S == 2 else None
+    stream = L.stream_and_check(hidden, w, cmap, ids, logit_mask, ids_out, conf, u)
+    a = L.LmUnmaskArgs(L.ptr(hidden), L.ptr(w), L.ptr(cmap), L.ptr(ids), L.ptr(ids_out), L.ptr(conf), L.ptr(u),
+                       sampler_args(top_k, top_p, temperature, seed, row_offset, position, logit_mask), B * Lq, Lq, D, V, S,
+                       int(mask_token_id), L.dtype_code(hidden.dtype))
+    L.check(L.get_lib().cad_lm_head_unmask(C.byref(a), stream), "cad_lm_head_unmask")
+    return (ids_out, conf, u) if return_u else (ids_out, conf)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # dense projections on the matrix cores (raw ops, no autograd: caduceus_amd/mixer.py schedules their gradients by hand)
 # ------------------------------------------------------------------------------------------------------------------

@@ -784,6 +784,46 @@ typedef struct cad_lm_score_args cad_lm_score_args;
 int cad_lm_head_score(const cad_lm_score_args* a, void* stream);
 int cad_lm_head_score_supported(int D, int V, int dtype);
 
+/* Unmask head: one round of iterative unmasking (masked infilling with a bi-directional or RCPS model) straight from the final hidden
+ * state, in one launch; neither logits nor log-probabilities are written per vocabulary entry.  Row i = b L + l of hidden is OPEN iff
+ * ids_in[i] == mask_id.
+ *   closed row   ids_out[i] = ids_in[i], conf[i] = 0.0f, u_out[i] = 0.0f; no logit is formed
+ *   open row     z          = the logit row cad_lm_head_fwd forms for row i (each strand's sum kept apart, then one commutative add)
+ *                x          = z + sampler.logit_mask
+ *                u          = the sampler's uniform with key sampler.seed and counter (sampler.row_offset + b, sampler.position + l)
+ *                ids_out[i] = the sampler's id for (x, top_k, top_p, temperature, u): rules 1 - 6 above cad_sampler_args, i.e. what
+ *                             cad_sample_tokens draws from row i of cad_lm_head_fwd's logits at that position and row offset
+ *                conf[i]    = x[id] - log-sum-exp of x over the allowed ids: the model's own log-probability of the id it drew, with
+ *                             temperature, top_k and top_p NOT applied -- what cad_lm_head_score gives for that target, bit for bit
+ *                u_out[i]   = u
+ * hidden: (S, rows, D) F32 / BF16 / F16.  weight: (V, D) fp32.  comp: S == 2 only.  ids_in, ids_out: (rows) int64; ids_out may be ids_in
+ * (a row has one reader, which is its one writer).  conf: (rows) fp32.  u_out: (rows) fp32 or NULL.  rows = B L with L given, so that
+ * a row's uniform depends on (seed, its sequence, its position) alone; sampler.position is the base added to l.  logit_mask must allow
+ * at least one id, and should not allow mask_id if the caller means rows to close.
+ * One launch on `stream`, no allocation, no synchronisation, no atomics, no shared memory: every output element has one writer, and a
+ * row's result does not depend on the rows around it.  cad_lm_head_unmask_supported: what cad_lm_head_score_supported serves (any D >= 1,
+ * 1 <= V <= 16, the three dtypes); anything else returns CAD_ERR_UNSUPPORTED before a launch; top_k < 0, top_p outside [0, 1] or
+ * temperature <= 0 CAD_ERR_BAD_ARG.  D 128 / 256 (512 in bf16) with a 16-byte aligned hidden run on the matrix cores on tiles of 16
+ * consecutive rows -- a tile without an open row is closed from its ids alone and its hidden rows are never loaded --, everything else
+ * one wave per open row. */
+struct cad_lm_unmask_args {
+    const void* hidden;
+    const float* weight;
+    const int64_t* comp;
+    const int64_t* ids_in;
+    int64_t* ids_out;
+    float* conf;
+    float* u_out;
+    cad_sampler_args sampler;
+    int64_t rows, L;
+    int D, V, n_strands;
+    int64_t mask_id;
+    int dtype;
+};
+typedef struct cad_lm_unmask_args cad_lm_unmask_args;
+int cad_lm_head_unmask(const cad_lm_unmask_args* a, void* stream);
+int cad_lm_head_unmask_supported(int D, int V, int dtype);
+
 /* ---------------------------------------------------------------------------------------------------------
  * hg38 data path -- the step in front of the model.
  *
