@@ -167,10 +167,9 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_kernel(cad_add_nor
             for (int w = 0; w < AN_WAVES; ++w) t += red[w][c];
             const int oc = a.swap_flip ? (D - 1 - c) : c;
             float* slot = pass == 0 ? wslots : bslots;
-            if (t != 0.f) {
-                if (slot) slot[(int64_t)blockIdx.x * D + oc] = t;
-                else atomicAdd(pass == 0 ? &a.dweight[oc] : &a.dbias[oc], t);
-            }
+            // a slot is WRITTEN by its workgroup, zeros included (+0 for a -0 sum, as a skipped store left it): the slots need no fill
+            if (slot) slot[(int64_t)blockIdx.x * D + oc] = t != 0.f ? t : 0.f;
+            else if (t != 0.f) atomicAdd(pass == 0 ? &a.dweight[oc] : &a.dbias[oc], t);
         }
         __syncthreads();
     }
@@ -408,10 +407,9 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add
             float t = 0.f;
             for (int w = 0; w < AN_WAVES; ++w) t += red[w][c];
             float* slot = pass == 0 ? wslots : bslots;
-            if (t != 0.f) {
-                if (slot) slot[(int64_t)blockIdx.x * D + c] = t;
-                else atomicAdd(pass == 0 ? &a.dweight[c] : &a.dbias[c], t);
-            }
+            // a slot is WRITTEN by its workgroup, zeros included (+0 for a -0 sum, as a skipped store left it): the slots need no fill
+            if (slot) slot[(int64_t)blockIdx.x * D + c] = t != 0.f ? t : 0.f;
+            else if (t != 0.f) atomicAdd(pass == 0 ? &a.dweight[c] : &a.dbias[c], t);
         }
         __syncthreads();
     }

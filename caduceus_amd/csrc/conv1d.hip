@@ -357,18 +357,15 @@ __global__ __launch_bounds__(CV_THREADS, CV_BWD_WAVES) void conv1d_bwd_kernel(Co
             if (k < a.K) {  // w[k] lives in w4[k + 4 - K]
                 float tot = 0.f;
                 for (int wv = 0; wv < CV_WAVES; ++wv) tot += red[wv][s][k + CV_KMAX - a.K];
-                if (tot != 0.f) {
-                    if (sets.wslots[s]) sets.wslots[s][(int64_t)blockIdx.y * a.E * a.K + e * a.K + k] = tot;
-                    else atomicAdd(&a.dw[e * a.K + k], tot);
-                }
+                // a slot is WRITTEN by its workgroup, zeros included (+0 for a -0 sum, as a skipped store left it): the slots need no fill
+                if (sets.wslots[s]) sets.wslots[s][(int64_t)blockIdx.y * a.E * a.K + e * a.K + k] = tot != 0.f ? tot : 0.f;
+                else if (tot != 0.f) atomicAdd(&a.dw[e * a.K + k], tot);
             }
         } else if (a.dbias) {
             float tot = 0.f;
             for (int wv = 0; wv < CV_WAVES; ++wv) tot += red[wv][s][CV_KMAX];
-            if (tot != 0.f) {
-                if (sets.bslots[s]) sets.bslots[s][(int64_t)blockIdx.y * a.E + e] = tot;
-                else atomicAdd(&a.dbias[e], tot);
-            }
+            if (sets.bslots[s]) sets.bslots[s][(int64_t)blockIdx.y * a.E + e] = tot != 0.f ? tot : 0.f;
+            else if (tot != 0.f) atomicAdd(&a.dbias[e], tot);
         }
     }
 }
@@ -492,6 +489,16 @@ extern "C" int cad_conv1d_bwd_multi_slotted(const cad_conv1d_bwd_args* sets, int
     const int st = conv1d_bwd_multi(sets, nsets, wslots, bslots, stream);
     if (st != 0) return st;
     const int n = cad_conv1d_bwd_slots(&sets[0]);
+    if (nsets == 2 && sets[0].K == sets[1].K && !sets[0].dbias == !sets[1].dbias) {
+        // both sets' folds of one kind in one launch (the same summation order: cad_reduce_partials_multi) -- two launches, not four
+        const cad_reduce_job wj[2] = {{wslots[0], sets[0].dw}, {wslots[1], sets[1].dw}};
+        int r = cad_reduce_partials_multi(wj, 2, n, (int64_t)sets[0].E * sets[0].K, CAD_F32, stream);
+        if (r == 0 && sets[0].dbias) {
+            const cad_reduce_job bj[2] = {{bslots[0], sets[0].dbias}, {bslots[1], sets[1].dbias}};
+            r = cad_reduce_partials_multi(bj, 2, n, sets[0].E, CAD_F32, stream);
+        }
+        return r;
+    }
     for (int i = 0; i < nsets; ++i) {
         int r = cad_reduce_partials(wslots[i], n, (int64_t)sets[i].E * sets[i].K, sets[i].dw, CAD_F32, stream);
         if (r == 0 && sets[i].dbias) r = cad_reduce_partials(bslots[i], n, sets[i].E, sets[i].dbias, CAD_F32, stream);

@@ -57,6 +57,50 @@ __global__ void reduce_partials_kernel(const typename cad_slot_of<T>::type* src,
     }
 }
 
+// Deep and narrow fp32 folds: the add + norm weight gradient of a long sequence is 1024 slots of d_model floats.  reduce_partials_kernel
+// gives every thread one 4-float column and ALL slots of it: 64 threads of the whole GPU walk 1 MB in 128 dependent rounds of loads
+// (0.27 ms per layer; the fold of a 0.23 ms kernel).  Here a workgroup owns RPD_VPB neighbouring columns (64 contiguous bytes of every
+// slot) and its threads the slot GROUPS of them: thread t sums the CAD_FOLD_GROUP slots of group t / RPD_VPB (+ 64, + 128, ...) in slot
+// order with all eight loads in flight, the group sums go through LDS, and one thread per column adds them in group order -- the
+// library's one summation order, bit-identical to reduce_partials_kernel.
+#define RPD_T 256
+#define RPD_VPB 4
+#define RPD_MAX_GROUPS 512   // 32 KB of LDS: slot depths up to 4096
+#define RPD_MIN_PARTS 64
+#define RPD_MAX_N 65536      // (a wide fold has a thread per column to fill the GPU with: reduce_partials_kernel)
+__global__ __launch_bounds__(RPD_T) void reduce_partials_deep_kernel(const float* src, int nparts, int64_t n, float* dst) {
+    struct __attribute__((aligned(16))) V4 { float f[4]; };
+    __shared__ V4 gs[RPD_MAX_GROUPS][RPD_VPB];
+    const int t = threadIdx.x, v = t % RPD_VPB;
+    const int64_t i = ((int64_t)blockIdx.x * RPD_VPB + v) * 4;  // (n % 4 == 0: i < n means the whole column is inside)
+    const int ngroups = (nparts + CAD_FOLD_GROUP - 1) / CAD_FOLD_GROUP;
+    if (i < n) {
+        for (int grp = t / RPD_VPB; grp < ngroups; grp += RPD_T / RPD_VPB) {
+            const int k0 = grp * CAD_FOLD_GROUP;
+            float x[CAD_FOLD_GROUP][4];
+#pragma unroll
+            for (int k = 0; k < CAD_FOLD_GROUP; ++k) {
+                if (k0 + k < nparts) ld4p<float>(src + (int64_t)(k0 + k) * n + i, x[k]);
+                else x[k][0] = x[k][1] = x[k][2] = x[k][3] = 0.f;
+            }
+            V4 g = {{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int k = 0; k < CAD_FOLD_GROUP; ++k)
+                if (k0 + k < nparts) g.f[0] += x[k][0], g.f[1] += x[k][1], g.f[2] += x[k][2], g.f[3] += x[k][3];
+            gs[grp][v] = g;
+        }
+    }
+    __syncthreads();
+    if (t < RPD_VPB && i < n) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int grp = 0; grp < ngroups; ++grp) {
+            const V4 g = gs[grp][v];
+            s[0] += g.f[0], s[1] += g.f[1], s[2] += g.f[2], s[3] += g.f[3];
+        }
+        cad_cvt_store<float, 4>(dst + i, s);
+    }
+}
+
 // several folds of the same depth and length in one launch (blockIdx.y = job): the dB and dC slots of both parameter sets of a layer
 struct ReduceJobs {
     const void* src[CAD_REDUCE_MAX_JOBS];
@@ -397,6 +441,12 @@ extern "C" int cad_fold_partials_stream(const cad_fold_args* sets, int nsets, in
 extern "C" int cad_reduce_partials(const void* src, int n_partials, int64_t n, void* dst, int dst_dtype, void* stream) {
     CAD_CHECK_ARG(src && dst && n_partials >= 1 && n > 0);
     const int vec = (n % 4) == 0 && (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
+    if (dst_dtype == CAD_F32 && vec && n <= RPD_MAX_N && n_partials >= RPD_MIN_PARTS &&
+        (n_partials + CAD_FOLD_GROUP - 1) / CAD_FOLD_GROUP <= RPD_MAX_GROUPS) {  // deep and narrow: the slot groups in parallel
+        dim3 grid((unsigned)((n / 4 + RPD_VPB - 1) / RPD_VPB)), block(RPD_T);
+        CAD_LAUNCH(reduce_partials_deep_kernel, grid, block, 0, stream, (const float*)src, n_partials, n, (float*)dst);
+        return cad_after_launch();
+    }
     int64_t nb = (n / 4 + 255) / 256 + 1;
     if (nb > 16384) nb = 16384;
     dim3 grid((unsigned)nb), block(256);

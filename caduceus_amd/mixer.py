@@ -98,7 +98,7 @@ def _conv_bwd2(x, params, douts, dx, split, dirs, bufs=None):
                                   split, E, wf.shape[1], dirs[i][0], dirs[i][1], L.dtype_code(x.dtype), 0)
         # per-workgroup slots of dw / dbias, folded by the library in a fixed order (ops.wgrad_slots): the same gradient every run
         ns = L.get_lib().cad_conv1d_bwd_slots(C.byref(args[i]))
-        ws, bs = ops.wgrad_slots(ns, dw.numel(), x.device), (None if db is None else ops.wgrad_slots(ns, E, x.device))
+        ws, bs = ops.wgrad_slots(ns, dw.numel(), x.device, zero=False), (None if db is None else ops.wgrad_slots(ns, E, x.device, zero=False))
         res.append((dw, db))
         slots.append((ws, bs))
     wptr = (C.c_void_p * n)(*[ws.data_ptr() for ws, _ in slots])

@@ -63,13 +63,14 @@ class _Embed(torch.autograd.Function):
         return None, dw.to(wdt), None, None, None
 
 
-def wgrad_slots(n_slots: int, n: int, device) -> torch.Tensor:
-    """Zeroed fp32 (n_slots, n): one slot per workgroup of a backward kernel for its share of a weight gradient (the cad_*_bwd_slotted
+def wgrad_slots(n_slots: int, n: int, device, zero: bool = True) -> torch.Tensor:
+    """fp32 (n_slots, n): one slot per workgroup of a backward kernel for its share of a weight gradient (the cad_*_bwd_slotted
     entry points), folded by the library in a fixed order instead of fp32 atomics in arrival order, so that the gradient -- and every
-    training step after it -- is the same in every run."""
+    training step after it -- is the same in every run.  zero=False: for the kernels whose every workgroup stores its whole slot (conv1d,
+    add + norm) -- no fill launch; the embedding's scalar kernel runs fewer workgroups than it has slots and keeps the fill."""
     if n_slots < 1:
         raise RuntimeError("caduceus_amd: a backward kernel reported no workgroups")
-    return torch.zeros((n_slots, n), dtype=torch.float32, device=device)
+    return (torch.zeros if zero else torch.empty)((n_slots, n), dtype=torch.float32, device=device)
 
 
 def embed(ids: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor], n_strands: int,
@@ -127,14 +128,15 @@ class _AddNorm(torch.autograd.Function):
         dres_out = None if dres_out is None else dres_out.contiguous()
         dx = torch.empty(res_out.shape, dtype=x_dtype, device=dy.device)
         dres_in = torch.empty(res_out.shape, dtype=torch.float32, device=dy.device) if has_res else None
-        dw = torch.zeros((D,), dtype=torch.float32, device=dy.device)
-        db = torch.zeros((D,), dtype=torch.float32, device=dy.device) if has_bias else None
+        # (dw / db are WRITTEN by the fold of the slots, the slots by their workgroups: nothing here needs a fill launch)
+        dw = torch.empty((D,), dtype=torch.float32, device=dy.device)
+        db = torch.empty((D,), dtype=torch.float32, device=dy.device) if has_bias else None
         stream = L.stream_and_check(dy, dres_out, res_out, rstd, mean, w, dx, dres_in, dw, db)
         a = L.AddNormBwdArgs(L.ptr(dy), L.ptr(dres_out), L.ptr(res_out), L.ptr(rstd), L.ptr(mean), L.ptr(w), L.ptr(dx),
                              L.ptr(dres_in), L.ptr(dw), L.ptr(db), rows, S, D, int(is_rms), int(swap_flip),
                              L.dtype_code(x_dtype), L.dtype_code(y_dtype))
         n = L.get_lib().cad_add_norm_bwd_slots(C.byref(a))
-        ws, bs = wgrad_slots(n, D, dy.device), (None if db is None else wgrad_slots(n, D, dy.device))
+        ws, bs = wgrad_slots(n, D, dy.device, zero=False), (None if db is None else wgrad_slots(n, D, dy.device, zero=False))
         L.check(L.get_lib().cad_add_norm_bwd_slotted(C.byref(a), L.ptr(ws), L.ptr(bs), stream), "cad_add_norm_bwd_slotted")
         return dx, dres_in, dw.to(wdt), (None if db is None else db.to(wdt)), None, None, None, None, None
 
@@ -205,13 +207,13 @@ class _Conv1d(torch.autograd.Function):
         E, SB, Lq = x.shape
         dout = dout.contiguous()
         dx = torch.empty_like(x)
-        dw = torch.zeros_like(wf)
-        db = torch.zeros((E,), dtype=torch.float32, device=x.device) if has_bias else None
+        dw = torch.empty_like(wf)  # (written by the fold of the slots)
+        db = torch.empty((E,), dtype=torch.float32, device=x.device) if has_bias else None
         stream = L.stream_and_check(x, wf, bf, dout, dx, dw, db)
         a = L.Conv1dBwdArgs(L.ptr(x), L.ptr(wf), L.ptr(bf), L.ptr(dout), L.ptr(dx), L.ptr(dw), L.ptr(db), SB, Lq, split,
                             E, wf.shape[1], rev_lo, rev_hi, L.dtype_code(x.dtype), 0)
         n = L.get_lib().cad_conv1d_bwd_slots(C.byref(a))
-        ws, bs = wgrad_slots(n, dw.numel(), x.device), (None if db is None else wgrad_slots(n, E, x.device))
+        ws, bs = wgrad_slots(n, dw.numel(), x.device, zero=False), (None if db is None else wgrad_slots(n, E, x.device, zero=False))
         L.check(L.get_lib().cad_conv1d_bwd_multi_slotted(C.byref(a), 1, (C.c_void_p * 1)(ws.data_ptr()),
                                                          (C.c_void_p * 1)(0 if bs is None else bs.data_ptr()), stream),
                 "cad_conv1d_bwd_multi_slotted")
