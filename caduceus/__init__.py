@@ -12,7 +12,7 @@ import sys
 
 import caduceus_amd as _impl
 
-for _name in ("configuration_caduceus", "modeling_caduceus", "modeling_rcps", "tokenization_caduceus", "scoring", "infilling"):
+for _name in ("configuration_caduceus", "modeling_caduceus", "modeling_rcps", "tokenization_caduceus", "scoring", "infilling", "embedding"):
     _mod = importlib.import_module("caduceus_amd." + _name)
     sys.modules[__name__ + "." + _name] = _mod
     globals()[_name] = _mod

@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CADUCEUS_AMD_LIB") or os.path.join(HERE, "libcaduceus_hip.so")
 
 CAD_F32, CAD_BF16, CAD_F16 = 0, 1, 2
+POOL_MEAN, POOL_MAX, POOL_WINDOW = 0, 1, 2
 PROF_KINDS = ("scan_fwd", "scan_bwd", "conv_fwd", "conv_bwd", "add_norm_fwd", "add_norm_bwd", "embed", "lm_head", "proj")
 
 _p = C.c_void_p
@@ -171,6 +172,12 @@ class LmUnmaskArgs(C.Structure):
                 ("dtype", _i)]
 
 
+class PoolHeadArgs(C.Structure):
+    _fields_ = [("x", _p), ("residual_in", _p), ("weight", _p), ("bias", _p), ("centre", _p), ("out", _p), ("scratch", _p),
+                ("B", _i64), ("L", _i64), ("half", _i64), ("S", _i), ("D", _i), ("eps", _f), ("is_rms", _i), ("x_dtype", _i),
+                ("y_dtype", _i), ("mode", _i)]
+
+
 # every exported symbol of include/caduceus_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "cad_version": (C.c_char_p, []),
@@ -247,6 +254,11 @@ SYMBOLS = {
     "cad_lm_head_score_supported": (_i, [_i, _i, _i]),
     "cad_lm_head_unmask": (_i, [C.POINTER(LmUnmaskArgs), _p]),
     "cad_lm_head_unmask_supported": (_i, [_i, _i, _i]),
+    "cad_pool_head": (_i, [C.POINTER(PoolHeadArgs), _p]),
+    "cad_pool_head_supported": (_i, [_i, _i, _i, _i, _i64]),
+    "cad_pool_head_scratch_floats": (_i64, [_i, _i64, _i64, _i, _i, _i64]),
+    "cad_pool_head_chunk_rows": (_i64, [_i, _i]),
+    "cad_pool_head_pieces": (_i64, [_i64, _i, _i64]),
     "cad_tokenize_mlm": (_i, [C.POINTER(MlmArgs), _p]),
     "cad_mlm_threshold": (C.c_uint32, [C.c_double]),
     "cad_hg38_interval": (_i, [_i64, _i64, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -138,8 +138,9 @@ class CaduceusMixerModel(nn.Module):
                                                                     **factory_kwargs)
         self.norm_f = norm_f if (config.fused_add_norm or not config.rcps) else RCPSAddNormWrapper(norm_f)
 
-    def forward_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None) -> torch.Tensor:
-        """Returns the final normed hidden state in the t-frame (S, B, L, D) in the compute dtype."""
+    def layers_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None):
+        """Embedding and layer loop without the final norm: (hidden (S, B, L, D), fp32 residual stream | None, compute dtype) -- the
+        operands of the final add + norm, which forward_tframe writes out and forward_tframe_pooled pools without writing."""
         if inputs_embeds is not None:
             act = act_dtype_of(inputs_embeds)
             hidden = engine.to_tframe(inputs_embeds, self.rcps)
@@ -162,13 +163,31 @@ class CaduceusMixerModel(nn.Module):
             if collect is not None:
                 collect.append(hidden)
             hidden, residual = layer.forward_tframe(hidden, residual, act)
+        return hidden, residual, act
+
+    def _final_norm_params(self):
         nf = self.norm_f.submodule if isinstance(self.norm_f, RCPSAddNormWrapper) else self.norm_f
-        w, b, eps, is_rms = norm_params(nf)
+        return norm_params(nf)
+
+    def forward_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None) -> torch.Tensor:
+        """Returns the final normed hidden state in the t-frame (S, B, L, D) in the compute dtype."""
+        hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds, collect)
+        w, b, eps, is_rms = self._final_norm_params()
         # final norm never swaps strands (modeling_caduceus.py:234-262)
         hidden, _ = ops.add_norm(hidden, residual, w, b, eps, is_rms, False, act)
         if collect is not None and self.fused_add_norm:  # reference quirk: appended only in the fused branch (:274-275)
             collect.append(hidden)
         return hidden
+
+    def forward_tframe_pooled(self, input_ids, inputs_embeds=None, mode: str = "mean", centre: Optional[torch.Tensor] = None,
+                              half: int = 0) -> torch.Tensor:
+        """forward_tframe followed by pooling over the sequence, as ONE pass over the last layer's output (ops.pool_head): the final
+        normed (S, B, L, D) activation is never written.  mode "mean" / "max" / "window" (centre (S, B) int64 t-frame positions, offsets
+        -half .. half, clamped).  Returns (S, B, D) fp32.  Inference only: no backward exists for the head."""
+        with torch.no_grad():
+            hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds)
+            w, b, eps, is_rms = self._final_norm_params()
+            return ops.pool_head(hidden, residual, w, b, eps, is_rms, act, mode, centre, half)
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         """{layer_idx: (conv_state, ssm_state)} of a causal stack (mamba_ssm MixerModel.allocate_inference_cache)."""
@@ -424,11 +443,14 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
     POOLINGS = ("mean", "max", "first", "last")
 
     def __init__(self, config: CaduceusConfig, pooling_strategy: str = "mean", conjoin_train: bool = False,
-                 conjoin_eval: bool = False, device=None, dtype=None, **kwargs):
+                 conjoin_eval: bool = False, device=None, dtype=None, fused_pool: bool = False, **kwargs):
         super().__init__(config, **kwargs)
         if pooling_strategy not in self.POOLINGS:
             raise NotImplementedError(f"Pooling strategy `{pooling_strategy}` not implemented.")
         self.pooling_strategy = pooling_strategy
+        # opt-in: with grad mode off the final norm and the pooling run as one pass (ops.pool_head; fp32 sums, no (S, B, L, D) normed
+        # tensor).  The head has no backward, so a forward with grad enabled takes the route through forward_tframe.
+        self.fused_pool = bool(fused_pool)
         self.num_labels = kwargs.get("num_labels", config.num_labels)
         self.caduceus = Caduceus(config, device=device, dtype=dtype, **kwargs)
         self.score = nn.Linear(config.d_model, self.num_labels, bias=False)
@@ -459,6 +481,14 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
         take_last = (how == "last") != reversed_positions
         return hidden_states.select(sequence_length_dim, -1 if take_last else 0)
 
+    def _pooled_tframe(self, input_ids, inputs_embeds):
+        """The pooling strategy through the pool head: (S, B, D) fp32, strand 1 pooled in ITS position order (first <-> last)."""
+        from .embedding import tframe_pooling
+        backbone = self.caduceus.backbone
+        like = input_ids if inputs_embeds is None else inputs_embeds
+        mode, centre, half = tframe_pooling(self.pooling_strategy, 2 if backbone.rcps else 1, like.shape[0], like.shape[1], like.device)
+        return backbone.forward_tframe_pooled(input_ids, inputs_embeds, mode, centre, half)
+
     def _sequence_loss(self, logits, labels):
         """HF convention (config.problem_type, inferred once from the label dtype / num_labels when unset)."""
         labels = labels.to(logits.device)
@@ -486,6 +516,7 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
             backbone = self.caduceus.backbone
             collect = [] if output_hidden_states else None
             conjoin = (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
+            fused = self.fused_pool and not torch.is_grad_enabled() and collect is None
             if conjoin:
                 if input_ids is None:
                     raise AssertionError("`input_ids` must be provided for conjoining.")
@@ -493,10 +524,16 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
                     raise AssertionError("`input_ids` must be 3D tensor: channels corresponds to forward and rc strands.")
                 B = input_ids.shape[0]
                 both = torch.cat([input_ids[..., 0], input_ids[..., 1]], dim=0)  # one pass over (2B, L)
-                t = backbone.forward_tframe(both, None, collect)[0]               # (2B, L, D)
-                pooled = [self.pool_hidden_states(t[:B]), self.pool_hidden_states(t[B:])]
+                if fused:
+                    p = self._pooled_tframe(both, None)[0]                        # (2B, D)
+                    pooled = [p[:B], p[B:]]
+                else:
+                    t = backbone.forward_tframe(both, None, collect)[0]           # (2B, L, D)
+                    pooled = [self.pool_hidden_states(t[:B]), self.pool_hidden_states(t[B:])]
                 if collect is not None:  # the reference reports the hidden states of its first (forward-strand) pass
                     collect = [h[:, :B] for h in collect]
+            elif fused:
+                pooled = list(self._pooled_tframe(input_ids, inputs_embeds if self.config.rcps else None))
             else:
                 t = backbone.forward_tframe(input_ids, inputs_embeds if self.config.rcps else None, collect)
                 pooled = [self.pool_hidden_states(t[0])]

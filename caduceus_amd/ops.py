@@ -827,6 +827,77 @@ def lm_head_unmask(hidden_t: torch.Tensor, weight: torch.Tensor, comp: Optional[
     return (ids_out, conf, u) if return_u else (ids_out, conf)
 
 
+class PoolUnsupported(ValueError):
+    """The pooling lies outside what cad_pool_head serves (d_model <= 1024; float32, bfloat16 or float16 activations; half < 2^22)."""
+
+
+POOL_MODES = {"mean": L.POOL_MEAN, "max": L.POOL_MAX, "window": L.POOL_WINDOW}
+_POOL_PAIRS = ((torch.float32, torch.float32), (torch.float32, torch.bfloat16), (torch.bfloat16, torch.bfloat16),
+               (torch.float32, torch.float16), (torch.float16, torch.float16))
+
+
+def pool_head_supported(D: int, x_dtype: torch.dtype, y_dtype: torch.dtype, mode: str = "mean", half: int = 0) -> bool:
+    if (x_dtype, y_dtype) not in _POOL_PAIRS or mode not in POOL_MODES:
+        return False
+    return bool(L.get_lib().cad_pool_head_supported(int(D), L.dtype_code(x_dtype), L.dtype_code(y_dtype), POOL_MODES[mode], int(half)))
+
+
+def pool_head(x: torch.Tensor, residual: Optional[torch.Tensor], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+              eps: float, is_rms: bool, y_dtype: torch.dtype, mode: str, centre: Optional[torch.Tensor] = None,
+              half: int = 0) -> torch.Tensor:
+    """Final add + norm and pooling over the sequence in one pass (cad_pool_head): x (S, B, L, D) is the last layer's t-frame output,
+    residual its fp32 residual stream or None; the normed rows are add_norm's (swap_flip off, rounded to y_dtype) and are never written.
+    mode "mean" / "max" pool all L rows; "window" averages rows clamp(centre[s, b] + k, 0, L - 1), k = -half .. half (the edge row
+    repeats; any int64 centre; half = 0 gathers one row).  weight None: no norm, the rows of x (+ residual) are pooled as they are.
+    Returns (S, B, D) fp32.  No autograd: tensors that require grad are refused while grad mode is on.  Arguments the kernel does not
+    serve raise PoolUnsupported."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"pool_head: mode is one of {sorted(POOL_MODES)}, got {mode!r}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, residual, weight, bias)):
+        raise RuntimeError("pool_head has no backward: call it under torch.no_grad() (or detach its inputs); the differentiable route is "
+                           "ops.add_norm followed by the pooling in torch")
+    if x.dim() != 4:
+        raise ValueError(f"pool_head: x is (S, B, L, D), got {tuple(x.shape)}")
+    S, B, Lq, D = x.shape
+    if S not in (1, 2) or B * Lq * D == 0:
+        raise ValueError(f"pool_head: x is (1 | 2, B, L, D) with at least one row, got {tuple(x.shape)}")
+    if weight is None and bias is not None:
+        raise ValueError("pool_head: a bias without a weight")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is not None and tuple(t.shape) != (D,):
+            raise ValueError(f"pool_head: {name} must be ({D},), got {tuple(t.shape)}")
+    if residual is not None:
+        if residual.dtype != torch.float32:
+            raise TypeError("caduceus_amd keeps the residual stream in fp32")
+        if residual.shape != x.shape:
+            raise ValueError(f"pool_head: residual must be {tuple(x.shape)}, got {tuple(residual.shape)}")
+    half = int(half)
+    if mode == "window":
+        if centre is None or centre.dtype != torch.int64 or tuple(centre.shape) != (S, B):
+            raise TypeError(f"pool_head: window pooling takes centre ({S}, {B}) int64")
+        if half < 0:
+            raise ValueError("pool_head: half >= 0")
+    elif centre is not None or half != 0:
+        raise ValueError(f"pool_head: centre and half belong to mode 'window', not {mode!r}")
+    if not pool_head_supported(D, x.dtype, y_dtype, mode, half):
+        raise PoolUnsupported(f"pool_head: cad_pool_head does not serve d_model {D}, x {x.dtype} -> y {y_dtype}, mode {mode!r}, half {half} "
+                              "(d_model <= 1024; the type pairs of add_norm; half < 2^22)")
+    x = x.detach().contiguous()
+    res = None if residual is None else residual.detach().contiguous()
+    w = None if weight is None else weight.detach().float().contiguous()
+    b = None if bias is None else bias.detach().float().contiguous()
+    cen = centre.contiguous() if mode == "window" else None
+    code = POOL_MODES[mode]
+    lib = L.get_lib()
+    out = torch.empty((S, B, D), dtype=torch.float32, device=x.device)
+    scratch = torch.empty((lib.cad_pool_head_scratch_floats(S, B, Lq, D, code, half),), dtype=torch.float32, device=x.device)
+    stream = L.stream_and_check(x, res, w, b, cen, out, scratch)
+    a = L.PoolHeadArgs(L.ptr(x), L.ptr(res), L.ptr(w), L.ptr(b), L.ptr(cen), L.ptr(out), L.ptr(scratch), B, Lq, half, S, D, float(eps),
+                       int(is_rms), L.dtype_code(x.dtype), L.dtype_code(y_dtype), code)
+    L.check(lib.cad_pool_head(C.byref(a), stream), "cad_pool_head")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # dense projections on the matrix cores (raw ops, no autograd: caduceus_amd/mixer.py schedules their gradients by hand)
 # ------------------------------------------------------------------------------------------------------------------

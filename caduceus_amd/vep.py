@@ -40,10 +40,13 @@ def window_mean(hidden: torch.Tensor, variant_idx: torch.Tensor, window_tokens: 
 
 @torch.no_grad()
 def embed_variants(backbone, batch: Dict[str, torch.Tensor], rcps: bool, bp_per_token: int = 1,
-                   autocast_dtype: Optional[torch.dtype] = torch.bfloat16) -> Dict[str, torch.Tensor]:
+                   autocast_dtype: Optional[torch.dtype] = torch.bfloat16, fused: bool = False) -> Dict[str, torch.Tensor]:
     """One step of vep_embeddings.py:352-392.  `backbone(input_ids)` returns the last hidden states (B, L, C) -- e.g.
     `lambda ids: model.caduceus(ids, return_dict=False)`.  batch: ref_input_ids, alt_input_ids, variant_idx and, for
-    non-RCPS models, ref_rc_input_ids / alt_rc_input_ids."""
+    non-RCPS models, ref_rc_input_ids / alt_rc_input_ids.
+    fused=True: `backbone` is a Caduceus model (Caduceus, CaduceusForMaskedLM, CaduceusForSequenceClassification) and the window means
+    come from embedding.pooled_embeddings -- final norm and window mean in one pass over the 2 x 1537 rows per sequence that matter,
+    summed in fp32, returned as float32; the last hidden states are never written.  The forwards stay one batch."""
     dev = next(iter(batch.values())).device if not hasattr(backbone, "parameters") else next(backbone.parameters()).device
     ids = [batch["alt_input_ids"], batch["ref_input_ids"]]
     if not rcps:
@@ -51,6 +54,20 @@ def embed_variants(backbone, batch: Dict[str, torch.Tensor], rcps: bool, bp_per_
     B = ids[0].shape[0]
     stacked = torch.cat([t.to(dev) for t in ids], 0)  # one launch sequence for all forwards of the step
     enabled = autocast_dtype is not None and dev.type == "cuda"
+    if fused:
+        from .embedding import backbone_of, pooled_embeddings
+        if rcps != bool(backbone_of(backbone).rcps):  # (a callable that is no Caduceus model: TypeError)
+            raise ValueError("embed_variants: `rcps` does not match the model's config")
+        v = batch["variant_idx"].to(dev)
+        # a reverse-complement INPUT (non-RCPS) is pooled where it lies: flipping its positions back moves the centre to L - 1 - v
+        centre = torch.cat([v, v] if rcps else [v, v, stacked.shape[1] - 1 - v, stacked.shape[1] - 1 - v], 0)
+        with torch.autocast(device_type=dev.type, dtype=autocast_dtype or torch.bfloat16, enabled=enabled):
+            out = pooled_embeddings(backbone, stacked, "window", centre=centre, window_tokens=WINDOW_SIZE_BP // bp_per_token)
+        if rcps:  # (2B, D, 2): [..., 1] is the reverse-complement strand back in the forward frame
+            alt, ref, alt_rc, ref_rc = out[:B, :, 0], out[B:, :, 0], out[:B, :, 1], out[B:, :, 1]
+        else:
+            alt, ref, alt_rc, ref_rc = out[:B], out[B:2 * B], out[2 * B:3 * B], out[3 * B:]
+        return {"concat_avg_ws": torch.cat([ref, alt], -1), "rc_concat_avg_ws": torch.cat([ref_rc, alt_rc], -1)}
     with torch.autocast(device_type=dev.type, dtype=autocast_dtype or torch.bfloat16, enabled=enabled):
         out = backbone(stacked)
     alt, ref = out[:B], out[B:2 * B]
@@ -78,15 +95,15 @@ def shard_batches(n_items: int, rank: int, world: int, batch_size: int) -> List[
 def dump_embeddings(backbone, dataset: Dict[str, torch.Tensor], rcps: bool, batch_size: int, rank: int = 0, world: int = 1,
                     bp_per_token: int = 1, passthrough: Iterable[str] = ("chromosome", "labels", "distance_to_nearest_tss",
                                                                          "tissue_embed"),
-                    autocast_dtype: Optional[torch.dtype] = torch.bfloat16) -> Dict[str, torch.Tensor]:
+                    autocast_dtype: Optional[torch.dtype] = torch.bfloat16, fused: bool = False) -> Dict[str, torch.Tensor]:
     """This rank's share of vep_embeddings.py:340-396 as one dict of CPU tensors (the caller saves / gathers it).
-    dataset: column name -> tensor with one row per variant."""
+    dataset: column name -> tensor with one row per variant.  fused: as embed_variants."""
     n = next(iter(dataset.values())).shape[0]
     store: Dict[str, List[torch.Tensor]] = {}
     for idx in shard_batches(n, rank, world, batch_size):
         sel = torch.tensor(idx)
         batch = {k: v[sel] for k, v in dataset.items()}
-        res = embed_variants(backbone, batch, rcps, bp_per_token, autocast_dtype)
+        res = embed_variants(backbone, batch, rcps, bp_per_token, autocast_dtype, fused)
         for k in passthrough:
             if k in batch:
                 store.setdefault(k, []).append(batch[k].cpu())

@@ -824,6 +824,53 @@ typedef struct cad_lm_unmask_args cad_lm_unmask_args;
 int cad_lm_head_unmask(const cad_lm_unmask_args* a, void* stream);
 int cad_lm_head_unmask_supported(int D, int V, int dtype);
 
+/* Pool head: pooled sequence embeddings straight from the last layer's output -- the final add + RMSNorm / LayerNorm and the pooling
+ * over the sequence in one pass over the pre-norm stream.  Neither the normed (S, B, L, D) activation nor a residual or rstd of it is
+ * written.
+ *   t[s,b,l,:]  = x[s,b,l,:] + residual_in[s,b,l,:]                       (fp32; x alone where residual_in is NULL)
+ *   y[s,b,l,:]  = the value cad_add_norm_fwd (swap_flip = 0) stores for that row: its statistics in its summation order, its scale,
+ *                 its rounding to y_dtype.  weight NULL: no norm at all, y = t (bias must be NULL too; y_dtype only has to form a
+ *                 served pair with x_dtype)
+ *   CAD_POOL_MEAN    out[s,b,:] = (1 / L) sum_l y[s,b,l,:]
+ *   CAD_POOL_MAX     out[s,b,:] = max_l y[s,b,l,:], a NaN propagating as in torch.max
+ *   CAD_POOL_WINDOW  out[s,b,:] = (1 / (2 half + 1)) sum_{k = -half .. half} y[s,b,clamp(centre[s,b] + k, 0, L - 1),:]
+ *                    clamping REPEATS the edge row (it does not shrink the window); any int64 centre is legal; only rows inside the
+ *                    window are read, the two edge rows weighted by their closed-form counts.  half = 0 is a one-row gather.
+ * x: (S, B, L, D) F32 / BF16 / F16, t-frame.  residual_in: fp32 or NULL.  weight, bias: (D) fp32, bias NULL for RMSNorm.  centre: (S, B)
+ * int64, WINDOW only.  out: (S, B, D) fp32.  scratch: cad_pool_head_scratch_floats(S, B, L, D, mode, half) floats, written before they
+ * are read (no fill needed).  (x_dtype, y_dtype): the five pairs of cad_add_norm_fwd.
+ * Two plain launches on `stream` (partials, then their fold), no allocation, no synchronisation, no atomics: every element has one
+ * writer.  The sums are fp32; their association order follows from (L, D, the dtypes, 16-byte alignment of the operands) -- and half for
+ * WINDOW -- alone: the rows of a (s, b) pair are walked from both ends at once (row lo + j with row hi - j, their two weighted values
+ * joined by one commutative add before anything else is summed) and cut into cad_pool_head_pieces(L, mode, half) pieces of whole chunks
+ * of cad_pool_head_chunk_rows(D, x_dtype) rows, one workgroup and one partial row per piece, folded in piece order.  A pair's bits depend
+ * neither on the pairs pooled beside it nor on the run, and they do not change when its rows are given in the opposite order (with the
+ * centre mirrored to L - 1 - centre): reverse-complementing the input of an RCPS model exchanges its two strands' pooled values exactly.
+ * cad_pool_head_supported: 1 <= D <= 1024, the five dtype pairs, the three modes, 0 <= half < 2^22; anything else returns
+ * CAD_ERR_UNSUPPORTED before a launch. */
+#define CAD_POOL_MEAN 0
+#define CAD_POOL_MAX 1
+#define CAD_POOL_WINDOW 2
+struct cad_pool_head_args {
+    const void* x;
+    const float* residual_in;
+    const float* weight;
+    const float* bias;
+    const int64_t* centre;
+    float* out;
+    float* scratch;
+    int64_t B, L, half;
+    int S, D;
+    float eps;
+    int is_rms, x_dtype, y_dtype, mode;
+};
+typedef struct cad_pool_head_args cad_pool_head_args;
+int cad_pool_head(const cad_pool_head_args* a, void* stream);
+int cad_pool_head_supported(int D, int x_dtype, int y_dtype, int mode, int64_t half);
+int64_t cad_pool_head_scratch_floats(int S, int64_t B, int64_t L, int D, int mode, int64_t half);
+int64_t cad_pool_head_chunk_rows(int D, int x_dtype);
+int64_t cad_pool_head_pieces(int64_t L, int mode, int64_t half);
+
 /* ---------------------------------------------------------------------------------------------------------
  * hg38 data path -- the step in front of the model.
  *
