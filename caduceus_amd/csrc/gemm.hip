@@ -380,6 +380,25 @@ struct GtCfg {
 static_assert(GtCfg::DPW == 2, "the counted waits below assume two DMA instructions per wave and chunk");
 static_assert((GtCfg::RING & (GtCfg::RING - 1)) == 0, "ring slots are advanced with a mask");
 
+// cad_glds16 with the streaming (nt) cache policy, for a channel-major operand that exactly ONE workgroup reads exactly once: the
+// [64 rows][128 tokens] ring chunks of the thin kernels and of cad_proj_xTw.  One production mixer layer, same box, three interleaved rounds,
+// average of its 16 projection launches: 0.1075 / 0.1084 / 0.1087 -> 0.1049 / 0.1054 / 0.1054 ms; in a traced step d(dt_lr) + dW_dt 73.9 ->
+// 54.5 us, x_proj 61.4 -> 54.8 us, out_proj unchanged (alone behind a 512 MiB fill: 0.209 -> 0.172 ms); profiles/r08_ab_proj_stream.txt.
+// The same policy LOSES wherever a second workgroup meets the lines in L2 and stays
+// off there (same file): the token-major X of cad_proj_wxT that the two row halves of in_proj share (+1.3 %), both operands of the
+// weight-gradient cad_gemm_stream (+3.7 %); neutral on the B operand of d(x2d) and on the addend of d(xc).
+__device__ __forceinline__ void gp_glds16_stream(const void* gsrc /* per lane */, uint32_t lds_base /* wave-uniform, SGPR */) {
+#ifdef CAD_EMU
+    cad_glds16(gsrc, lds_base);
+#else
+    uint32_t keep;  // (M0: as cad_glds16)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_base)
+                 : "memory");
+#endif
+}
+
 template <typename TE>
 __device__ __forceinline__ void gt_issue_chunk(const TE* X, int64_t ldx, int k0, int64_t t0, int64_t T, char* xbuf, int wave,
                                                int lane) {
@@ -391,7 +410,7 @@ __device__ __forceinline__ void gt_issue_chunk(const TE* X, int64_t ldx, int k0,
         const int lp = (((pp >> 1) ^ gx_swz(row)) << 1) | (pp & 1);  // logical piece = 8 tokens
         int64_t tok = t0 + lp * 8;
         tok = tok + 8 <= T ? tok : T - 8;                            // tail block: valid data, never stored
-        cad_glds16(X + (int64_t)(k0 + row) * ldx + tok, cad_uniform((int)(cad_lds_off(xbuf) + ins * 1024)));
+        gp_glds16_stream(X + (int64_t)(k0 + row) * ldx + tok, cad_uniform((int)(cad_lds_off(xbuf) + ins * 1024)));
     }
 }
 
