@@ -1,8 +1,9 @@
-// fp16 siblings of the MFMA projection entry points (include/caduceus_hip.h, cad_*_f16): the kernel templates of gemm.hip instantiated
-// for binary16 operands (v_mfma_f32_16x16x32_f16, the same operand packing as the bf16 instruction; fp32 accumulation; results rounded
-// to nearest even, +-inf beyond 65504).  A translation unit of its own, so that each object holds the kernels of one element type.
-#define CAD_GEMM_TEMPLATES_ONLY
-#include "gemm.hip"
+// fp16 siblings of the MFMA projection entry points (include/caduceus_hip.h, cad_*_f16): the kernel templates of gemm.hip's three headers
+// instantiated for binary16 operands (v_mfma_f32_16x16x32_f16, the same operand packing as the bf16 instruction; fp32 accumulation; results
+// rounded to nearest even, +-inf beyond 65504).  A translation unit of its own, so that each object holds the kernels of one element type.
+#include "proj_wstat.h"
+#include "proj_ring.h"
+#include "gemm_stream.h"
 
 extern "C" int cad_proj_wxT_f16(const cad_proj_args* a, void* stream) { return proj_wxT<f16_t>(a, stream); }
 extern "C" int cad_proj_wx_f16(const cad_proj_args* a, void* stream) { return proj_wx<f16_t>(a, stream); }

@@ -1,5 +1,5 @@
 // fp8 (OCP e4m3) in_proj on the matrix cores (include/caduceus_hip.h: cad_quant_rows_fp8, cad_proj_wxT_fp8) -- BASELINE
-// configs[4] "fp8 MFMA projections".  Same skeleton as proj_wxT_kernel (gemm.hip): W-stationary B fragments in registers
+// configs[4] "fp8 MFMA projections".  Same skeleton as proj_wxT_kernel (proj_wstat.h): W-stationary B fragments in registers
 // for the whole launch, X by LDS-DMA in 64-token blocks (double buffered, XOR-swizzled 16-byte pieces), a D lane's four
 // consecutive tokens through a per-wave staging tile into 16-byte channel-major stores -- with
 //   * v_mfma_f32_16x16x32_fp8_fp8: the same 32-deep K step per instruction as the bf16 form at half the operand bytes (an

@@ -15,7 +15,7 @@ duplicated in/out projections.  Here:
 On THIS (generic, per-op autograd) path the dense projections go through ops.mm (fp32, and fp16 on its exact fp32 widening: the own
 cad_gemm_f32; bf16: the own strided MFMA GEMM cad_gemm_b16 when _OWN_GEMM_B16 is on, torch.mm / hipBLASLt when it is off -- the kernel has not been timed against the library yet, so the conservative default is off);
 the production configuration (tied, "add") runs mixer.BiMambaMixerFn instead, whose projections are the library's own MFMA kernels
-(csrc/gemm.hip) -- no library GEMM on that step.
+(csrc/gemm.hip; the kernels in its headers proj_wstat.h, proj_ring.h, gemm_stream.h) -- no library GEMM on that step.
 """
 from __future__ import annotations
 

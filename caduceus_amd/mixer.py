@@ -14,7 +14,7 @@ readable specification).  Scheduling the backward by hand removes what generic a
 BiMambaMixerFn.forward / backward read as the schedule; every step of it is one module-level stage function (_in_proj ... _dW_in_partials)
 that owns its dispatch chain: the own kernel if it serves the shape, else the next kernel, else the GEMM library through torch.
 All kernels are the C-ABI entry points of include/caduceus_hip.h.  At the benchmarked shapes (bf16, d_model 256 / 512) EVERY product runs
-on the library's own MFMA kernels (csrc/gemm.hip, gemm_fp8.hip): in_proj, x_proj, dt_proj (+ bias + softplus), out_proj, d(y), d(dt_lr) +
+on the library's own MFMA kernels (csrc/gemm.hip and its headers proj_wstat.h / proj_ring.h / gemm_stream.h, gemm_fp8.hip): in_proj, x_proj, dt_proj (+ bias + softplus), out_proj, d(y), d(dt_lr) +
 dW_dt (one pass, cad_proj_wx_wgrad), dW_x, d(xc), d(x2d), dW_in and dW_out; fp32 takes cad_gemm_f32, and only bf16 / fp16 shapes that no
 own kernel serves reach hipBLASLt through torch.
 Scan launches with fewer workgroups than the GPU has CUs are L-split (ops.lsplit_factor).
@@ -310,7 +310,7 @@ def _in_proj(x2d, W_in, w_in, cache, fp8_act):
     if _in_proj_is_streamed(Dm, x2d.dtype):
         # A = tokens, B = W_in^T, channel-major result (None if the shape is not served)
         xz = ops.gemm_out_t(x2d, _transposed(cache, "w_inT", w_in))
-    if xz is None and ops.proj_supported(x2d, Dm):  # bf16: the W-stationary MFMA kernel (csrc/gemm.hip) writes channel-major directly
+    if xz is None and ops.proj_supported(x2d, Dm):  # bf16: the W-stationary MFMA kernel (csrc/proj_wstat.h) writes channel-major directly
         xz = ops.proj_wxT(w_in, x2d)
     if xz is None:
         xz = ops.mm(w_in, x2d.t())  # fp32: cad_gemm_f32; a bf16 shape no own kernel serves: the library
@@ -336,7 +336,7 @@ def _dt_proj(w_dt, dt_lr, dt_bias):
     (delta_is_dt) -- delta_bias + softplus in the epilogue of an HBM-bound kernel with idle VALU instead of the scan prologues; from the
     library plain W_dt dt_lr, and the scans add the bias and apply the softplus."""
     R, T = dt_lr.shape
-    if ops.proj_wx_supported(dt_lr, R, T):  # thin-K MFMA kernel (transposing LDS reads), csrc/gemm.hip
+    if ops.proj_wx_supported(dt_lr, R, T):  # thin-K MFMA kernel (transposing LDS reads), csrc/proj_wstat.h
         return ops.proj_wx(w_dt, dt_lr, softplus_bias=dt_bias), True
     return ops.mm(w_dt, dt_lr), False
 

@@ -915,21 +915,30 @@ def mm_f32(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
     N = b.shape[1]
     n = _f32_kslices(M, N, K) if b.shape[0] == K else 1  # (a shape mismatch is reported by _gemm_f32)
     if n > 1:
-        Kc = K // n
-        part = _gemm_f32(a.unflatten(1, (n, Kc)).permute(1, 0, 2), b.unflatten(0, (n, Kc)), None, None)  # (n, M, N)
-        res = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        if (M * N) % 4 == 0:
-            fold_f32([(part, res, M * N, n, M * N, 1, 0)])
-        else:
-            torch.sum(part, dim=0, out=res)
-        if addend is not None:
-            res = res + addend
-        if out is None:
-            return res
-        out.copy_(res)
-        return out
+        return _mm_kslices("gemm_f32", torch.float32, torch.float32, a, b, n, out, addend)
     return _gemm_f32(a.unsqueeze(0), b.unsqueeze(0), None if out is None else out.unsqueeze(0),
                      None if addend is None else addend.unsqueeze(0))[0]
+
+
+def _mm_kslices(name, in_dtype, out_dtype, a, b, n, out, addend):
+    """The K-slice branch of mm_f32 / mm_b16: the n slices in ONE batched launch with fp32 partial tiles, summed in fp32 in slice order
+    (fold_f32; torch.sum where M * N is no multiple of 4), the addend added in fp32, ONE rounding to out_dtype (the type of `out`)."""
+    M, K = a.shape
+    N = b.shape[1]
+    Kc = K // n
+    part = _gemm_strided(name, in_dtype, torch.float32, a.unflatten(1, (n, Kc)).permute(1, 0, 2), b.unflatten(0, (n, Kc)),
+                         None, None)  # (n, M, N) fp32
+    res = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    if (M * N) % 4 == 0:
+        fold_f32([(part, res, M * N, n, M * N, 1, 0)])
+    else:
+        torch.sum(part, dim=0, out=res)
+    if addend is not None:
+        res = res + addend.float()
+    if out is None:
+        return res.to(out_dtype)
+    out.copy_(res)
+    return out
 
 
 def _f32_kslices(M: int, N: int, K: int) -> int:
@@ -1062,20 +1071,7 @@ def mm_b16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
     N = b.shape[1]
     n = _f32_kslices(M, N, K) if b.shape[0] == K else 1  # (a shape mismatch is reported by _gemm_strided)
     if n > 1:
-        Kc = K // n
-        part = _gemm_strided("gemm_b16", torch.bfloat16, torch.float32, a.unflatten(1, (n, Kc)).permute(1, 0, 2), b.unflatten(0, (n, Kc)),
-                             None, None)  # (n, M, N) fp32
-        res = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        if (M * N) % 4 == 0:
-            fold_f32([(part, res, M * N, n, M * N, 1, 0)])
-        else:
-            torch.sum(part, dim=0, out=res)
-        if addend is not None:
-            res = res + addend.float()
-        if out is None:
-            return res.to(torch.bfloat16)
-        out.copy_(res)
-        return out
+        return _mm_kslices("gemm_b16", torch.bfloat16, torch.bfloat16, a, b, n, out, addend)
     return _gemm_strided("gemm_b16", torch.bfloat16, torch.bfloat16, a.unsqueeze(0), b.unsqueeze(0), None if out is None else out.unsqueeze(0),
                          None if addend is None else addend.unsqueeze(0))[0]
 
@@ -1149,7 +1145,10 @@ def bmm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.bmm(a, b)
 
 
-# 16-bit element types of the MFMA projection kernels (csrc/gemm.hip): each cad_proj_* / cad_gemm_stream entry point has an fp16 sibling
+# ------------------------------------------------------------------------------------------------------------------
+# the 16-bit (bf16 / fp16) MFMA projections: csrc/gemm.hip, gemm_f16.hip and their headers proj_wstat.h, proj_ring.h
+# ------------------------------------------------------------------------------------------------------------------
+# 16-bit element types of the MFMA projection kernels: each cad_proj_* / cad_gemm_stream entry point has an fp16 sibling
 _MFMA_DTYPES = (torch.bfloat16, torch.float16)
 
 
@@ -1224,13 +1223,6 @@ def proj_wx(W: torch.Tensor, X: torch.Tensor, out: Optional[torch.Tensor] = None
     return out
 
 
-# ------------------------------------------------------------------------------------------------------------------
-# fp8 (OCP e4m3) in_proj: BASELINE configs[4] "fp8 MFMA projections"
-# ------------------------------------------------------------------------------------------------------------------
-FP8 = torch.float8_e4m3fn
-FP8_MAX = 448.0
-
-
 def proj_xTw_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
     return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_xTw_supported(int(M), int(K), int(T)))
 
@@ -1250,6 +1242,62 @@ def proj_xTw(W: torch.Tensor, X: torch.Tensor, X2: Optional[torch.Tensor] = None
     return out
 
 
+def proj_wx_wgrad_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
+    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wx_wgrad_supported(int(M), int(K), int(T)))
+
+
+def wgrad_partials(T: int, K: int, M: int, device, nsets: int = 1) -> torch.Tensor:
+    """(nsets, P, K, M) fp32 partial slots of cad_proj_wx_wgrad, one (K, M) slot per workgroup: a caller with several parameter sets
+    hands each launch its own [i] and folds all of them with ONE sum over dim 1 afterwards."""
+    return torch.empty((nsets, L.get_lib().cad_proj_wx_wgrad_partials(T), K, M), dtype=torch.float32, device=device)
+
+
+def proj_wx_wgrad(W: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  part: Optional[torch.Tensor] = None):
+    """(out (M, T) = W (M, K) @ X (K, T),  dW (K, M) fp32 = X (K, T) @ Y (M, T)^T) from ONE pass over X (cad_proj_wx_wgrad):
+    d(dt_lr) = W_dt^T d(delta) together with dW_dt = d(delta) dt_lr^T.  All operands channel-major bf16.
+    part: a (P, K, M) slice of wgrad_partials() -- then the partial slots are left un-summed (returns (out, None))."""
+    M, K = W.shape
+    T = X.shape[1]
+    if X.shape[0] != K or Y.shape != (M, T) or W.stride(1) != 1 or X.stride(1) != 1 or Y.stride(1) != 1:
+        raise ValueError("proj_wx_wgrad: W (M, K), X (K, T), Y (M, T) with unit inner stride")
+    _same_mfma_dtype(W, X, Y, out)
+    if out is None:
+        out = torch.empty((M, T), dtype=X.dtype, device=X.device)
+    own = part is None
+    if own:
+        part = wgrad_partials(T, K, M, X.device)[0]
+    stream = L.stream_and_check(W, X, Y, out, part, contiguous=False)
+    a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0), None, 0, None, 0,
+                   L.ptr(Y), Y.stride(0), L.ptr(part))
+    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
+    return out, (part.sum(dim=0) if own else None)
+
+
+def proj_wgrad_only_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
+    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wgrad_only_supported(int(M), int(K), int(T)))
+
+
+def proj_wgrad_only(X: torch.Tensor, Y: torch.Tensor, part: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """dW (M, K) fp32 = Y (M, T) @ X (K, T)^T, both channel-major bf16, M <= 64: the weight-gradient stage of cad_proj_wx_wgrad
+    alone (W == NULL) -- dW_x = d(dbc) . xc^T of the x_proj backward.  part: as for proj_wx_wgrad (slots hold the (K, M) transpose)."""
+    K, T = X.shape
+    M = Y.shape[0]
+    if Y.shape[1] != T or X.stride(1) != 1 or Y.stride(1) != 1:
+        raise ValueError("proj_wgrad_only: X (K, T), Y (M, T) with unit inner stride")
+    _same_mfma_dtype(X, Y)
+    own = part is None
+    if own:
+        part = wgrad_partials(T, K, M, X.device)[0]
+    stream = L.stream_and_check(X, Y, part, contiguous=False)
+    a = L.ProjArgs(None, L.ptr(X), None, T, M, K, 0, X.stride(0), 0, None, 0, None, 0, L.ptr(Y), Y.stride(0), L.ptr(part))
+    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
+    return part.sum(dim=0).t().contiguous() if own else None
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the streamed tiled GEMM (csrc/gemm_stream.h) and the fp32 folds of partial tiles (csrc/fold_f32.hip)
+# ------------------------------------------------------------------------------------------------------------------
 GEMM_PARTIALS, GEMM_OUT_T_BF16 = 0, 1
 
 
@@ -1327,6 +1375,13 @@ def proj_xTw_stream(Wt: torch.Tensor, X: torch.Tensor, col_fastest: bool = False
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# fp8 (OCP e4m3) in_proj: BASELINE configs[4] "fp8 MFMA projections"
+# ------------------------------------------------------------------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
 def fp8_proj_supported(t: torch.Tensor, K: int) -> bool:
     return t.dtype in (torch.bfloat16, torch.float32) and bool(L.get_lib().cad_proj_fp8_supported(int(K)))
 
@@ -1370,59 +1425,6 @@ def proj_wxT_fp8(Wq: torch.Tensor, sw: torch.Tensor, Xq: torch.Tensor, sx: torch
                       out.stride(0))
     L.check(L.get_lib().cad_proj_wxT_fp8(C.byref(a), stream), "cad_proj_wxT_fp8")
     return out
-
-
-def proj_wx_wgrad_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
-    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wx_wgrad_supported(int(M), int(K), int(T)))
-
-
-def wgrad_partials(T: int, K: int, M: int, device, nsets: int = 1) -> torch.Tensor:
-    """(nsets, P, K, M) fp32 partial slots of cad_proj_wx_wgrad, one (K, M) slot per workgroup: a caller with several parameter sets
-    hands each launch its own [i] and folds all of them with ONE sum over dim 1 afterwards."""
-    return torch.empty((nsets, L.get_lib().cad_proj_wx_wgrad_partials(T), K, M), dtype=torch.float32, device=device)
-
-
-def proj_wx_wgrad(W: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, out: Optional[torch.Tensor] = None,
-                  part: Optional[torch.Tensor] = None):
-    """(out (M, T) = W (M, K) @ X (K, T),  dW (K, M) fp32 = X (K, T) @ Y (M, T)^T) from ONE pass over X (cad_proj_wx_wgrad):
-    d(dt_lr) = W_dt^T d(delta) together with dW_dt = d(delta) dt_lr^T.  All operands channel-major bf16.
-    part: a (P, K, M) slice of wgrad_partials() -- then the partial slots are left un-summed (returns (out, None))."""
-    M, K = W.shape
-    T = X.shape[1]
-    if X.shape[0] != K or Y.shape != (M, T) or W.stride(1) != 1 or X.stride(1) != 1 or Y.stride(1) != 1:
-        raise ValueError("proj_wx_wgrad: W (M, K), X (K, T), Y (M, T) with unit inner stride")
-    _same_mfma_dtype(W, X, Y, out)
-    if out is None:
-        out = torch.empty((M, T), dtype=X.dtype, device=X.device)
-    own = part is None
-    if own:
-        part = wgrad_partials(T, K, M, X.device)[0]
-    stream = L.stream_and_check(W, X, Y, out, part, contiguous=False)
-    a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, W.stride(0), X.stride(0), out.stride(0), None, 0, None, 0,
-                   L.ptr(Y), Y.stride(0), L.ptr(part))
-    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
-    return out, (part.sum(dim=0) if own else None)
-
-
-def proj_wgrad_only_supported(X: torch.Tensor, M: int, K: int, T: int) -> bool:
-    return X.dtype in _MFMA_DTYPES and bool(L.get_lib().cad_proj_wgrad_only_supported(int(M), int(K), int(T)))
-
-
-def proj_wgrad_only(X: torch.Tensor, Y: torch.Tensor, part: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
-    """dW (M, K) fp32 = Y (M, T) @ X (K, T)^T, both channel-major bf16, M <= 64: the weight-gradient stage of cad_proj_wx_wgrad
-    alone (W == NULL) -- dW_x = d(dbc) . xc^T of the x_proj backward.  part: as for proj_wx_wgrad (slots hold the (K, M) transpose)."""
-    K, T = X.shape
-    M = Y.shape[0]
-    if Y.shape[1] != T or X.stride(1) != 1 or Y.stride(1) != 1:
-        raise ValueError("proj_wgrad_only: X (K, T), Y (M, T) with unit inner stride")
-    _same_mfma_dtype(X, Y)
-    own = part is None
-    if own:
-        part = wgrad_partials(T, K, M, X.device)[0]
-    stream = L.stream_and_check(X, Y, part, contiguous=False)
-    a = L.ProjArgs(None, L.ptr(X), None, T, M, K, 0, X.stride(0), 0, None, 0, None, 0, L.ptr(Y), Y.stride(0), L.ptr(part))
-    L.check(_proj_fn("cad_proj_wx_wgrad", X.dtype)(C.byref(a), stream), "cad_proj_wx_wgrad")
-    return part.sum(dim=0).t().contiguous() if own else None
 
 
 # ------------------------------------------------------------------------------------------------------------------

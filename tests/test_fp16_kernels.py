@@ -281,7 +281,7 @@ def test_lm_head_f16_hidden(backend, n_strands, V, D, B, L):
     torch.testing.assert_close(wd.grad.cpu(), rw.grad, rtol=2e-3, atol=2e-3)
 
 
-# ---- the MFMA projections (csrc/gemm.hip): each mode against an fp32 product of the same fp16 operands ----------------------------------
+# ---- the MFMA projections (csrc/gemm_f16.hip on the headers of csrc/gemm.hip): each mode against an fp32 product of the same fp16 operands ----------------------------------
 def _operands(shapes, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return [(scale * torch.randn(*s, generator=g)).to(F16).float() for s in shapes]

@@ -1,4 +1,4 @@
-"""The hand-written MFMA projection kernels (csrc/gemm.hip) against fp32 matrix products of the same bf16 operands, on
+"""The hand-written MFMA projection kernels (csrc/gemm.hip and its headers proj_wstat.h, proj_ring.h, gemm_stream.h) against fp32 matrix products of the same bf16 operands, on
 the host emulator (MFMA / LDS-DMA semantics restated in tests/emu + cad_common.h) and on the GPU."""
 import pytest
 import torch
@@ -442,6 +442,146 @@ def test_gemm_out_t_as_a_projection_with_column_tiles_fastest(backend, M, K, T):
     perm = torch.randperm(T, generator=torch.Generator().manual_seed(6))
     out_p = ops.gemm_out_t(X[perm].contiguous().to(dev), Wt.to(dev))
     assert torch.equal(out.cpu()[:, perm], out_p.cpu())
+
+
+# ---- the exported shape predicates (csrc/gemm.hip) against the entry points that consult them, at the predicates' edges --------------
+_UNSUPPORTED = 2   # CAD_ERR_UNSUPPORTED (include/caduceus_hip.h)
+_SENT16, _SENT32 = 77.0, -3.0  # what the output buffers hold before the call (exact in bf16 / fp32)
+
+
+def _edge_cases():
+    """(family, shape, branch).  branch restates what include/caduceus_hip.h documents for the shape: "ok", "shape" (a shape rule refuses
+    it) or "lds" (inside the shape rules, but the W copy next to the 64 KB ring of X tiles does not fit the 160 KB of LDS)."""
+    t128 = lambda T: T >= 128 and T % 128 == 0
+    t8 = lambda T: T >= 8 and T % 8 == 0
+    cases = []
+    for M in (1, 16, 17, 64, 65):
+        for K in (256, 512, 192):
+            for T in (128, 256, 136):
+                cases.append(("wgrad_only", (M, K, T), "ok" if 1 <= M <= 64 and K in (256, 512) and t128(T) else "shape"))
+    for M in (16, 32, 48):
+        for K in (256, 512):
+            for T in (128, 136):
+                cases.append(("wx_wgrad", (M, K, T), "ok" if M in (16, 32) and t128(T) else "shape"))
+    for M, K in ((1, 128), (64, 1024), (65, 128), (48, 1088), (16, 64)):
+        for T in (8, 136):
+            if not (1 <= M <= 64 and 64 < K <= 1024 and K % 64 == 0 and t8(T)):
+                cases.append(("thin", (M, K, T), "shape"))
+            else:
+                cases.append(("thin", (M, K, T), "ok" if 64 * 1024 + (M + 15) // 16 * 16 * K * 2 <= 160 * 1024 else "lds"))
+    for M in (128, 256, 64):
+        for K in (256, 512, 128):
+            for T in (8, 12):
+                cases.append(("xTw", (M, K, T), "ok" if M in (128, 256) and K in (256, 512) and t8(T) else "shape"))
+    for R, Cc in ((256, 256), (256, 128)):
+        for K, n in ((32, 1), (48, 1), (64, 2)):
+            cases.append(("gemm_stream", (R, Cc, K, n), "ok" if Cc % 256 == 0 and (K // n) % 32 == 0 else "shape"))
+    return cases
+
+
+_EDGE_CASES = _edge_cases()
+
+
+def _pitched(rows, cols, seed, dev, scale=1.0):
+    """A (rows, cols) bf16 operand whose row pitch is a multiple of 8 elements (16-byte aligned rows, as the kernels require)."""
+    full = (_bf(rows, (cols + 7) // 8 * 8, seed=seed) * scale).to(dev)
+    return full[:, :cols]
+
+
+def _run_edge_case(lib, dev, family, shape):
+    """Calls the predicate and the entry point with valid, aligned operands and sentinel-filled outputs.
+    -> (predicate, status, [(output, sentinel)], verify) with verify() holding the outputs to the fp32 product of the bf16 operands."""
+    from caduceus_amd import _lib as L
+    import ctypes as C
+    f32 = lambda t: t.float().cpu()
+    if family in ("wgrad_only", "wx_wgrad"):
+        M, K, T = shape
+        prod = family == "wx_wgrad"
+        pred = (lib.cad_proj_wx_wgrad_supported if prod else lib.cad_proj_wgrad_only_supported)(M, K, T)
+        X, Y = _pitched(K, T, 61, dev), _pitched(M, T, 62, dev)
+        W = (_bf(M, K, seed=63) * 0.2).to(dev) if prod else None
+        out = torch.full((M, T), _SENT16, dtype=torch.bfloat16, device=dev) if prod else None
+        part = torch.full((lib.cad_proj_wx_wgrad_partials(T), K, M), _SENT32, dtype=torch.float32, device=dev)
+        stream = L.stream_and_check(X, Y, W, out, part, contiguous=False)
+        a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, K if prod else 0, X.stride(0), T if prod else 0, None, 0, None, 0,
+                       L.ptr(Y), Y.stride(0), L.ptr(part))
+        status = lib.cad_proj_wx_wgrad(C.byref(a), stream)
+
+        def verify():
+            ref = f32(X) @ f32(Y).t()  # (K, M)
+            if prod:  # (the tolerances of test_proj_wx_thin_m_deep_k / test_proj_wx_wgrad_fused)
+                po = f32(W) @ f32(X)
+                torch.testing.assert_close(f32(out), po.to(torch.bfloat16).float(), rtol=2e-2, atol=2e-2 * float(po.abs().max()) / 4)
+                torch.testing.assert_close(part.sum(0).cpu(), ref, rtol=1e-4, atol=1e-4 * float(ref.abs().max()))
+            else:     # (test_proj_wgrad_only)
+                torch.testing.assert_close(part.sum(0).cpu(), ref, rtol=1e-4, atol=1e-3 * (T / 128) ** 0.5)
+        return pred, status, [(part, _SENT32)] + ([(out, _SENT16)] if prod else []), verify
+    if family == "thin":
+        M, K, T = shape
+        pred = lib.cad_proj_wx_thin_supported(M, K, T)
+        thin_k = bool(lib.cad_proj_wx_supported(K, T))  # cad_proj_wx then runs the thin-K kernel
+        W, X = (_bf(M, K, seed=64) * (1.0 if thin_k else 0.2)).to(dev), _pitched(K, T, 65, dev)
+        out = torch.full((M, T), _SENT16, dtype=torch.bfloat16, device=dev)
+        stream = L.stream_and_check(W, X, out, contiguous=False)
+        a = L.ProjArgs(L.ptr(W), L.ptr(X), L.ptr(out), T, M, K, K, X.stride(0), T, None, 0)
+        status = lib.cad_proj_wx(C.byref(a), stream)
+
+        def verify():  # (test_proj_wx for the thin-K kernel, test_proj_wx_thin_m_deep_k for the thin-M one)
+            ref = f32(W) @ f32(X)
+            torch.testing.assert_close(f32(out), ref.to(torch.bfloat16).float(), rtol=2e-2,
+                                       atol=2e-2 if thin_k else 2e-2 * float(ref.abs().max()) / 4)
+        return pred, status, [(out, _SENT16)], verify
+    if family == "xTw":
+        M, K, T = shape
+        pred = lib.cad_proj_xTw_supported(M, K, T)
+        W, X = _bf(M, K, seed=66).to(dev), _pitched(K, T, 67, dev)
+        out = torch.full((T, M), _SENT16, dtype=torch.bfloat16, device=dev)
+        stream = L.stream_and_check(W, X, out, contiguous=False)
+        a = L.ProjTmArgs(L.ptr(W), L.ptr(X), None, L.ptr(out), T, M, K, K, X.stride(0), M)
+        status = lib.cad_proj_xTw(C.byref(a), stream)
+
+        def verify():  # (test_proj_xTw_token_major_out_proj)
+            ref = f32(X).t() @ f32(W).t()
+            torch.testing.assert_close(f32(out), ref, rtol=1e-2, atol=1e-2 * float(ref.abs().max()) / 8)
+            torch.testing.assert_close(f32(out), ref.to(torch.bfloat16).float(), rtol=2e-2, atol=2e-2 * float(ref.abs().max()) / 8)
+        return pred, status, [(out, _SENT16)], verify
+    R, Cc, K, n = shape
+    pred = lib.cad_gemm_stream_supported(R, Cc, K, n)
+    A, B = _bf(R, K, seed=68).to(dev), _bf(K, Cc, seed=69).to(dev)
+    part = torch.full((n, R, Cc), _SENT32, dtype=torch.float32, device=dev)
+    stream = L.stream_and_check(A, B, part, contiguous=False)
+    a = L.GemmStreamArgs(L.ptr(A), L.ptr(B), L.ptr(part), R, Cc, K, K, Cc, 0, n, ops.GEMM_PARTIALS)
+    status = lib.cad_gemm_stream(C.byref(a), stream)
+
+    def verify():  # (test_gemm_stream_weight_gradient_partials)
+        ref = f32(A) @ f32(B)
+        torch.testing.assert_close(part.sum(0).cpu(), ref, rtol=1e-4, atol=1e-4 * float(ref.abs().max()))
+    return pred, status, [(part, _SENT32)], verify
+
+
+@pytest.mark.parametrize("family,shape,branch", _EDGE_CASES, ids=[f"{f}-{'x'.join(map(str, s))}" for f, s, _ in _EDGE_CASES])
+def test_shape_predicates_agree_with_the_entry_points_at_their_edges(backend, family, shape, branch):
+    """The *_supported predicates are stated once (csrc/gemm.hip) and the templated launchers of both element types call that statement:
+    at every edge of a predicate the entry point must say the same.  Predicate 0: CAD_ERR_UNSUPPORTED and not one byte written
+    (sentinel-filled outputs) -- except that cad_proj_wx serves a shape the thin-M predicate refuses through its thin-K kernel where
+    cad_proj_wx_supported holds ((16, 64)).  Predicate 1: status 0 and the fp32 product of the same bf16 operands, within the tolerance
+    this file uses for that kernel.  Shapes: the smallest that reach each edge."""
+    from caduceus_amd import _lib as L
+    # every branch of the predicates occurs in the list: both verdicts per predicate, and the one LDS bound that binds inside the shape
+    # rules (thin M / deep K: 64 x 1024 of W next to the ring; the weight-gradient forms stay below 160 KB at every admitted shape)
+    seen = {f: {b for g, _, b in _EDGE_CASES if g == f} for f in ("wgrad_only", "wx_wgrad", "thin", "xTw", "gemm_stream")}
+    assert all({"ok", "shape"} <= s for s in seen.values()) and "lds" in seen["thin"], seen
+    lib, dev = L.get_lib(), backend[1]
+    pred, status, outputs, verify = _run_edge_case(lib, dev, family, shape)
+    assert pred == int(branch == "ok"), (family, shape, branch, pred)
+    if pred or (family == "thin" and lib.cad_proj_wx_supported(shape[1], shape[2])):
+        assert family != "thin" or pred or shape[:2] == (16, 64)
+        assert status == 0, (family, shape, status)
+        verify()
+    else:
+        assert status == _UNSUPPORTED, (family, shape, status)
+        for t, sentinel in outputs:
+            assert bool((t == sentinel).all()), (family, shape, "an unsupported call wrote its output")
 
 
 # ---- cad_gemm_f32: the fp32 path's dense products on the fp32 matrix core (csrc/gemm_f32.hip) ---------------------------------------

@@ -1,4 +1,4 @@
-"""The MFMA projections (csrc/gemm.hip, gemm_fp8.hip, gemm_f32.hip) held to EXACT sums, with several blocks per workgroup.
+"""The MFMA projections (csrc/gemm.hip with its headers proj_wstat.h / proj_ring.h / gemm_stream.h, gemm_fp8.hip, gemm_f32.hip) held to EXACT sums, with several blocks per workgroup.
 
 A  exact sums: integer operands whose partial sums stay below 2^24 in any order (asserted from abs(L) @ abs(R)), so fp32 accumulation is
    exact whatever the MFMA's internal order: 16-bit outputs must equal the fp64 product rounded ONCE to nearest even, bit for bit, fp32

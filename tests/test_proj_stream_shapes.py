@@ -1,4 +1,4 @@
-"""The ring-chunk loaders of csrc/gemm.hip after the change of their cache policy (streaming LDS-DMA loads of the channel-major operand):
+"""The ring-chunk loaders of csrc/proj_ring.h after the change of their cache policy (streaming LDS-DMA loads of the channel-major operand):
 cad_proj_wx thin M / deep K, cad_proj_wx_wgrad (fused and weight gradient alone) and cad_proj_xTw at the real channel counts
 (D = 256, E = 512, R + 2N = 48, R = 16), bit for bit against the exact sums of tests/test_proj_exact.py (integer operands whose partial
 sums stay below 2^24 in any order: the fp64 product rounded once IS the result, whatever moves the bytes).

@@ -23,7 +23,7 @@ VARIANTS = {
     # cad_glds16 is shared with the scans' prefetch (measured there: noise)
     "nt_dma_loads": [("cad_common.h",) + _DMA_NT],
     # ... the projection kernels only (the candidate for adoption: measured -0.4 ms per step for the family with nt_dma_loads, while nt on
-    # the scans' prefetch alone was noise): a streaming twin of cad_glds16 in cad_stream.h, used by every DMA of gemm.hip / gemm_fp8.hip
+    # the scans' prefetch alone was noise): a streaming twin of cad_glds16 in cad_stream.h, used by every DMA of gemm.hip's headers / gemm_fp8.hip
     "nt_proj_x_loads": [
         ("cad_stream.h", "template <int FAMILY, typename V>\n__device__ __forceinline__ void cad_store_stream(V* p, V v) {",
          "__device__ __forceinline__ void cad_glds16_stream(const void* gsrc, uint32_t lds_base) {\n"
@@ -31,7 +31,9 @@ VARIANTS = {
          '    asm volatile("s_mov_b32 %0, m0\\n\\ts_mov_b32 m0, %2\\n\\ts_nop 0\\n\\tglobal_load_lds_dwordx4 %1, off nt\\n\\ts_mov_b32 m0, %0"\n'
          '                 : "=&s"(keep)\n                 : "v"(gsrc), "s"(lds_base)\n                 : "memory");\n#endif\n}\n'
          "template <int FAMILY, typename V>\n__device__ __forceinline__ void cad_store_stream(V* p, V v) {"),
-        ("gemm.hip", "__ALL__cad_glds16(", "cad_glds16_stream("),
+        ("proj_wstat.h", "__ALL__cad_glds16(", "cad_glds16_stream("),
+        ("proj_ring.h", "__ALL__cad_glds16(", "cad_glds16_stream("),
+        ("gemm_stream.h", "__ALL__cad_glds16(", "cad_glds16_stream("),
         ("gemm_fp8.hip", "__ALL__cad_glds16(", "cad_glds16_stream("),
     ],
     # ordinary stores everywhere (the state before csrc/cad_stream.h)
