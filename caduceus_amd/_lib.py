@@ -178,6 +178,12 @@ class PoolHeadArgs(C.Structure):
                 ("y_dtype", _i), ("mode", _i)]
 
 
+class PoolHeadBwdArgs(C.Structure):
+    _fields_ = [("x", _p), ("residual_in", _p), ("weight", _p), ("bias", _p), ("centre", _p), ("g", _p), ("out", _p), ("dx", _p),
+                ("dres_in", _p), ("dweight", _p), ("dbias", _p), ("rows", _p), ("scratch", _p), ("B", _i64), ("L", _i64), ("half", _i64),
+                ("S", _i), ("D", _i), ("eps", _f), ("is_rms", _i), ("x_dtype", _i), ("y_dtype", _i), ("mode", _i)]
+
+
 # every exported symbol of include/caduceus_hip.h: name -> (restype, argtypes)
 SYMBOLS = {
     "cad_version": (C.c_char_p, []),
@@ -259,6 +265,11 @@ SYMBOLS = {
     "cad_pool_head_scratch_floats": (_i64, [_i, _i64, _i64, _i, _i, _i64]),
     "cad_pool_head_chunk_rows": (_i64, [_i, _i]),
     "cad_pool_head_pieces": (_i64, [_i64, _i, _i64]),
+    "cad_pool_head_bwd": (_i, [C.POINTER(PoolHeadBwdArgs), _p]),
+    "cad_pool_head_max_rows": (_i, [C.POINTER(PoolHeadBwdArgs), _p, _p, _p, _p]),
+    "cad_pool_head_bwd_supported": (_i, [_i, _i, _i, _i, _i64]),
+    "cad_pool_head_bwd_scratch_floats": (_i64, [_i, _i64, _i64, _i, _i, _i64]),
+    "cad_pool_head_bwd_pieces": (_i64, [_i64]),
     "cad_tokenize_mlm": (_i, [C.POINTER(MlmArgs), _p]),
     "cad_mlm_threshold": (C.c_uint32, [C.c_double]),
     "cad_hg38_interval": (_i, [_i64, _i64, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),

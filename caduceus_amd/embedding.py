@@ -9,6 +9,7 @@ and a window centre c becomes L - 1 - c; mean and max do not care.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -62,18 +63,19 @@ def tframe_pooling(pooling: str, S: int, B: int, L: int, device, centre: Optiona
 
 
 def pooled_embeddings(model, input_ids: torch.Tensor, pooling: str = "mean", *, centre: Optional[torch.Tensor] = None,
-                      window_tokens: Optional[int] = None) -> torch.Tensor:
+                      window_tokens: Optional[int] = None, grad: bool = False) -> torch.Tensor:
     """Sequence embeddings of input_ids (B, L): the model's last hidden states pooled over the sequence, fp32.
     pooling: "mean", "max", "first", "last", or "window" -- the mean over positions centre[b] + [-w // 2, w // 2] with w = window_tokens,
     clamped to [0, L - 1] so that an edge token repeats (vep.window_mean); centre is (B,) int64, any value.
     Returns (B, D), or (B, D, 2) for an RCPS model (see the module docstring for the frame).  Runs under the model's precision scope and
-    torch.no_grad(); reads nothing back from the device."""
+    torch.no_grad(); reads nothing back from the device.  grad=True follows the ambient grad mode instead: the embeddings then
+    back-propagate into the model through the pool head's backward (ops.pool_head_grad)."""
     backbone = backbone_of(model)
     if input_ids.dim() != 2:
         raise ValueError(f"pooled_embeddings: input_ids is (B, L), got {tuple(input_ids.shape)}")
     B, L = input_ids.shape
     S = 2 if backbone.rcps else 1
-    with torch.no_grad(), model._precision_scope():
+    with contextlib.nullcontext() if grad else torch.no_grad(), model._precision_scope():
         mode, cen, half = tframe_pooling(pooling, S, B, L, input_ids.device, centre, window_tokens)
-        out = backbone.forward_tframe_pooled(input_ids, None, mode, cen, half)  # (S, B, D)
+        out = backbone.forward_tframe_pooled(input_ids, None, mode, cen, half, grad=grad)  # (S, B, D)
     return out[0] if S == 1 else out.permute(1, 2, 0)

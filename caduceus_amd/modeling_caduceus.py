@@ -180,14 +180,16 @@ class CaduceusMixerModel(nn.Module):
         return hidden
 
     def forward_tframe_pooled(self, input_ids, inputs_embeds=None, mode: str = "mean", centre: Optional[torch.Tensor] = None,
-                              half: int = 0) -> torch.Tensor:
+                              half: int = 0, grad: bool = False) -> torch.Tensor:
         """forward_tframe followed by pooling over the sequence, as ONE pass over the last layer's output (ops.pool_head): the final
         normed (S, B, L, D) activation is never written.  mode "mean" / "max" / "window" (centre (S, B) int64 t-frame positions, offsets
-        -half .. half, clamped).  Returns (S, B, D) fp32.  Inference only: no backward exists for the head."""
-        with torch.no_grad():
+        -half .. half, clamped).  Returns (S, B, D) fp32.  By default it runs under torch.no_grad(); grad=True follows the ambient grad
+        mode and pools through ops.pool_head_grad, whose backward recomputes the rows instead of saving them."""
+        with contextlib.nullcontext() if grad else torch.no_grad():
             hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds)
             w, b, eps, is_rms = self._final_norm_params()
-            return ops.pool_head(hidden, residual, w, b, eps, is_rms, act, mode, centre, half)
+            head = ops.pool_head_grad if grad else ops.pool_head
+            return head(hidden, residual, w, b, eps, is_rms, act, mode, centre, half)
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         """{layer_idx: (conv_state, ssm_state)} of a causal stack (mamba_ssm MixerModel.allocate_inference_cache)."""
@@ -443,7 +445,8 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
     POOLINGS = ("mean", "max", "first", "last")
 
     def __init__(self, config: CaduceusConfig, pooling_strategy: str = "mean", conjoin_train: bool = False,
-                 conjoin_eval: bool = False, device=None, dtype=None, fused_pool: bool = False, **kwargs):
+                 conjoin_eval: bool = False, device=None, dtype=None, fused_pool: bool = False, fused_pool_train: bool = False,
+                 **kwargs):
         super().__init__(config, **kwargs)
         if pooling_strategy not in self.POOLINGS:
             raise NotImplementedError(f"Pooling strategy `{pooling_strategy}` not implemented.")
@@ -451,6 +454,8 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
         # opt-in: with grad mode off the final norm and the pooling run as one pass (ops.pool_head; fp32 sums, no (S, B, L, D) normed
         # tensor).  The head has no backward, so a forward with grad enabled takes the route through forward_tframe.
         self.fused_pool = bool(fused_pool)
+        # opt-in on top of it: the pool head under grad as well (ops.pool_head_grad), so that training and evaluation pool alike
+        self.fused_pool_train = bool(fused_pool_train)
         self.num_labels = kwargs.get("num_labels", config.num_labels)
         self.caduceus = Caduceus(config, device=device, dtype=dtype, **kwargs)
         self.score = nn.Linear(config.d_model, self.num_labels, bias=False)
@@ -487,7 +492,7 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
         backbone = self.caduceus.backbone
         like = input_ids if inputs_embeds is None else inputs_embeds
         mode, centre, half = tframe_pooling(self.pooling_strategy, 2 if backbone.rcps else 1, like.shape[0], like.shape[1], like.device)
-        return backbone.forward_tframe_pooled(input_ids, inputs_embeds, mode, centre, half)
+        return backbone.forward_tframe_pooled(input_ids, inputs_embeds, mode, centre, half, grad=self.fused_pool_train)
 
     def _sequence_loss(self, logits, labels):
         """HF convention (config.problem_type, inferred once from the label dtype / num_labels when unset)."""
@@ -516,7 +521,7 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
             backbone = self.caduceus.backbone
             collect = [] if output_hidden_states else None
             conjoin = (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
-            fused = self.fused_pool and not torch.is_grad_enabled() and collect is None
+            fused = (self.fused_pool_train or (self.fused_pool and not torch.is_grad_enabled())) and collect is None
             if conjoin:
                 if input_ids is None:
                     raise AssertionError("`input_ids` must be provided for conjoining.")

@@ -842,52 +842,40 @@ def pool_head_supported(D: int, x_dtype: torch.dtype, y_dtype: torch.dtype, mode
     return bool(L.get_lib().cad_pool_head_supported(int(D), L.dtype_code(x_dtype), L.dtype_code(y_dtype), POOL_MODES[mode], int(half)))
 
 
-def pool_head(x: torch.Tensor, residual: Optional[torch.Tensor], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-              eps: float, is_rms: bool, y_dtype: torch.dtype, mode: str, centre: Optional[torch.Tensor] = None,
-              half: int = 0) -> torch.Tensor:
-    """Final add + norm and pooling over the sequence in one pass (cad_pool_head): x (S, B, L, D) is the last layer's t-frame output,
-    residual its fp32 residual stream or None; the normed rows are add_norm's (swap_flip off, rounded to y_dtype) and are never written.
-    mode "mean" / "max" pool all L rows; "window" averages rows clamp(centre[s, b] + k, 0, L - 1), k = -half .. half (the edge row
-    repeats; any int64 centre; half = 0 gathers one row).  weight None: no norm, the rows of x (+ residual) are pooled as they are.
-    Returns (S, B, D) fp32.  No autograd: tensors that require grad are refused while grad mode is on.  Arguments the kernel does not
-    serve raise PoolUnsupported."""
-    if mode not in POOL_MODES:
-        raise ValueError(f"pool_head: mode is one of {sorted(POOL_MODES)}, got {mode!r}")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, residual, weight, bias)):
-        raise RuntimeError("pool_head has no backward: call it under torch.no_grad() (or detach its inputs); the differentiable route is "
-                           "ops.add_norm followed by the pooling in torch")
+def _pool_head_checked(who, x, residual, weight, bias, y_dtype, mode, centre, half):
+    """The argument checks pool_head and pool_head_grad share -> (S, B, L, D, half)."""
     if x.dim() != 4:
-        raise ValueError(f"pool_head: x is (S, B, L, D), got {tuple(x.shape)}")
+        raise ValueError(f"{who}: x is (S, B, L, D), got {tuple(x.shape)}")
     S, B, Lq, D = x.shape
     if S not in (1, 2) or B * Lq * D == 0:
-        raise ValueError(f"pool_head: x is (1 | 2, B, L, D) with at least one row, got {tuple(x.shape)}")
+        raise ValueError(f"{who}: x is (1 | 2, B, L, D) with at least one row, got {tuple(x.shape)}")
     if weight is None and bias is not None:
-        raise ValueError("pool_head: a bias without a weight")
+        raise ValueError(f"{who}: a bias without a weight")
     for name, t in (("weight", weight), ("bias", bias)):
         if t is not None and tuple(t.shape) != (D,):
-            raise ValueError(f"pool_head: {name} must be ({D},), got {tuple(t.shape)}")
+            raise ValueError(f"{who}: {name} must be ({D},), got {tuple(t.shape)}")
     if residual is not None:
         if residual.dtype != torch.float32:
             raise TypeError("caduceus_amd keeps the residual stream in fp32")
         if residual.shape != x.shape:
-            raise ValueError(f"pool_head: residual must be {tuple(x.shape)}, got {tuple(residual.shape)}")
+            raise ValueError(f"{who}: residual must be {tuple(x.shape)}, got {tuple(residual.shape)}")
     half = int(half)
     if mode == "window":
         if centre is None or centre.dtype != torch.int64 or tuple(centre.shape) != (S, B):
-            raise TypeError(f"pool_head: window pooling takes centre ({S}, {B}) int64")
+            raise TypeError(f"{who}: window pooling takes centre ({S}, {B}) int64")
         if half < 0:
-            raise ValueError("pool_head: half >= 0")
+            raise ValueError(f"{who}: half >= 0")
     elif centre is not None or half != 0:
-        raise ValueError(f"pool_head: centre and half belong to mode 'window', not {mode!r}")
+        raise ValueError(f"{who}: centre and half belong to mode 'window', not {mode!r}")
     if not pool_head_supported(D, x.dtype, y_dtype, mode, half):
-        raise PoolUnsupported(f"pool_head: cad_pool_head does not serve d_model {D}, x {x.dtype} -> y {y_dtype}, mode {mode!r}, half {half} "
+        raise PoolUnsupported(f"{who}: cad_pool_head does not serve d_model {D}, x {x.dtype} -> y {y_dtype}, mode {mode!r}, half {half} "
                               "(d_model <= 1024; the type pairs of add_norm; half < 2^22)")
-    x = x.detach().contiguous()
-    res = None if residual is None else residual.detach().contiguous()
-    w = None if weight is None else weight.detach().float().contiguous()
-    b = None if bias is None else bias.detach().float().contiguous()
-    cen = centre.contiguous() if mode == "window" else None
-    code = POOL_MODES[mode]
+    return S, B, Lq, D, half
+
+
+def _pool_head_fwd(x, res, w, b, cen, eps, is_rms, y_dtype, code, half):
+    """cad_pool_head on detached, contiguous operands (w / b fp32) -> out (S, B, D) fp32."""
+    S, B, Lq, D = x.shape
     lib = L.get_lib()
     out = torch.empty((S, B, D), dtype=torch.float32, device=x.device)
     scratch = torch.empty((lib.cad_pool_head_scratch_floats(S, B, Lq, D, code, half),), dtype=torch.float32, device=x.device)
@@ -896,6 +884,89 @@ def pool_head(x: torch.Tensor, residual: Optional[torch.Tensor], weight: Optiona
                        int(is_rms), L.dtype_code(x.dtype), L.dtype_code(y_dtype), code)
     L.check(lib.cad_pool_head(C.byref(a), stream), "cad_pool_head")
     return out
+
+
+def pool_head(x: torch.Tensor, residual: Optional[torch.Tensor], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+              eps: float, is_rms: bool, y_dtype: torch.dtype, mode: str, centre: Optional[torch.Tensor] = None,
+              half: int = 0) -> torch.Tensor:
+    """Final add + norm and pooling over the sequence in one pass (cad_pool_head): x (S, B, L, D) is the last layer's t-frame output,
+    residual its fp32 residual stream or None; the normed rows are add_norm's (swap_flip off, rounded to y_dtype) and are never written.
+    mode "mean" / "max" pool all L rows; "window" averages rows clamp(centre[s, b] + k, 0, L - 1), k = -half .. half (the edge row
+    repeats; any int64 centre; half = 0 gathers one row).  weight None: no norm, the rows of x (+ residual) are pooled as they are.
+    Returns (S, B, D) fp32.  No autograd: tensors that require grad are refused while grad mode is on (pool_head_grad is the
+    differentiable form).  Arguments the kernel does not serve raise PoolUnsupported."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"pool_head: mode is one of {sorted(POOL_MODES)}, got {mode!r}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, residual, weight, bias)):
+        raise RuntimeError("pool_head has no backward: call it under torch.no_grad() (or detach its inputs); the differentiable route is "
+                           "ops.add_norm followed by the pooling in torch")
+    S, B, Lq, D, half = _pool_head_checked("pool_head", x, residual, weight, bias, y_dtype, mode, centre, half)
+    x = x.detach().contiguous()
+    res = None if residual is None else residual.detach().contiguous()
+    w = None if weight is None else weight.detach().float().contiguous()
+    b = None if bias is None else bias.detach().float().contiguous()
+    cen = centre.contiguous() if mode == "window" else None
+    return _pool_head_fwd(x, res, w, b, cen, eps, is_rms, y_dtype, POOL_MODES[mode], half)
+
+
+class _PoolHead(torch.autograd.Function):
+    """cad_pool_head with cad_pool_head_bwd behind it.  Saved: the inputs, and `out` for MAX (the rows its gradient goes to are found
+    from it in the backward); no statistic, y or dy of size L exists in either direction."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, centre, eps, is_rms, y_dtype, code, half):
+        xc = x.detach().contiguous()
+        res = None if residual is None else residual.detach().contiguous()
+        w = None if weight is None else weight.detach().float().contiguous()
+        b = None if bias is None else bias.detach().float().contiguous()
+        out = _pool_head_fwd(xc, res, w, b, centre, eps, is_rms, y_dtype, code, half)
+        ctx.save_for_backward(xc, res, weight, bias, centre, out if code == L.POOL_MAX else None)
+        ctx.cfg = (float(eps), int(is_rms), y_dtype, code, half)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, res, weight, bias, cen, out = ctx.saved_tensors
+        eps, is_rms, y_dtype, code, half = ctx.cfg
+        S, B, Lq, D = x.shape
+        lib = L.get_lib()
+        dev = x.device
+        w = None if weight is None else weight.detach().float().contiguous()
+        b = None if bias is None else bias.detach().float().contiguous()
+        g = g.detach().float().contiguous()
+        need_w = weight is not None and ctx.needs_input_grad[2]
+        need_b = bias is not None and ctx.needs_input_grad[3]
+        dx = torch.empty_like(x)
+        dres = None if res is None else torch.empty_like(res)
+        dw = torch.empty((D,), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty((D,), dtype=torch.float32, device=dev) if need_b else None
+        is_max = code == L.POOL_MAX
+        rows = torch.empty((S, B, D), dtype=torch.int64, device=dev) if is_max else None
+        scratch = None
+        if is_max or need_w or need_b:
+            scratch = torch.empty((lib.cad_pool_head_bwd_scratch_floats(S, B, Lq, D, code, half),), dtype=torch.float32, device=dev)
+        stream = L.stream_and_check(x, res, w, b, cen, g, out, dx, dres, dw, db, rows, scratch)
+        a = L.PoolHeadBwdArgs(L.ptr(x), L.ptr(res), L.ptr(w), L.ptr(b), L.ptr(cen), L.ptr(g), L.ptr(out), L.ptr(dx), L.ptr(dres), L.ptr(dw),
+                              L.ptr(db), L.ptr(rows), L.ptr(scratch), B, Lq, half, S, D, eps, is_rms, L.dtype_code(x.dtype),
+                              L.dtype_code(y_dtype), code)
+        L.check(lib.cad_pool_head_bwd(C.byref(a), stream), "cad_pool_head_bwd")
+        return (dx if ctx.needs_input_grad[0] else None, dres if ctx.needs_input_grad[1] else None,
+                dw.to(weight.dtype) if need_w else None, db.to(bias.dtype) if need_b else None, None, None, None, None, None, None)
+
+
+def pool_head_grad(x: torch.Tensor, residual: Optional[torch.Tensor], weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                   eps: float, is_rms: bool, y_dtype: torch.dtype, mode: str, centre: Optional[torch.Tensor] = None,
+                   half: int = 0) -> torch.Tensor:
+    """pool_head with a backward (cad_pool_head_bwd): the same arguments and checks, the same cad_pool_head call -- so the same bits --
+    and gradients for x, residual, weight and bias.  Only the inputs are saved (and `out` for "max"): the backward recomputes each row's
+    add and statistics and writes dx (x's dtype) and d(residual) (fp32) in one pass; the rounding of the normed rows to y_dtype is
+    straight-through, as in add_norm; "max" sends a channel's gradient to the lowest row that attains the maximum, as torch.max does.
+    d(weight) / d(bias) come back in the parameters' dtype, run-to-run identical."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"pool_head_grad: mode is one of {sorted(POOL_MODES)}, got {mode!r}")
+    S, B, Lq, D, half = _pool_head_checked("pool_head_grad", x, residual, weight, bias, y_dtype, mode, centre, half)
+    cen = centre.contiguous() if mode == "window" else None
+    return _PoolHead.apply(x, residual, weight, bias, cen, eps, is_rms, y_dtype, POOL_MODES[mode], half)
 
 
 # ------------------------------------------------------------------------------------------------------------------

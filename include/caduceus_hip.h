@@ -871,6 +871,54 @@ int64_t cad_pool_head_scratch_floats(int S, int64_t B, int64_t L, int D, int mod
 int64_t cad_pool_head_chunk_rows(int D, int x_dtype);
 int64_t cad_pool_head_pieces(int64_t L, int mode, int64_t half);
 
+/* Pool head backward: the gradient of cad_pool_head from the forward's own operands -- nothing is saved by the forward, and neither y, dy
+ * nor a statistic of size L is written.  x, residual_in, weight, bias, centre and the parameters are the forward's; g: (S, B, D) fp32, the
+ * gradient of out.  Per row r of pair (s, b), with t = x + residual_in (fp32), mean / rstd the forward's statistics of the row and
+ * xh = (t - mean) rstd:
+ *   dy[c]  = m(r) (g[s,b,c] / n)     MEAN / WINDOW: n = L or 2 half + 1, one IEEE division per (s, b, c); m(r) the multiplicity the forward
+ *                                    gives the row (1; the closed-form counts on rows 0 and L - 1 of a window; 0 outside the window), an
+ *                                    exact integer, one rounded product
+ *            g[s,b,c] on row rows[s,b,c], 0 elsewhere     MAX: rows as cad_pool_head_max_rows finds them
+ *   gw = dy w,  sgx = mean_c(gw xh),  sg = mean_c(gw) (0 for RMSNorm),  dt = rstd (gw - sg - xh sgx)        (cad_add_norm_bwd's sequence; the
+ *                                    rounding of y to y_dtype is straight-through; weight NULL: dt = dy)
+ *   dres_in[s,b,r,:] = dt (fp32),  dx[s,b,r,:] = dt rounded to x_dtype;  dweight[c] = sum dy xh,  dbias[c] = sum dy over all rows of all pairs.
+ * dx: (S, B, L, D) x_dtype.  dres_in: fp32, non-NULL exactly when residual_in is.  dweight, dbias: (D) fp32, WRITTEN, each may be NULL; both
+ * NULL when weight is NULL.  Every element of dx / dres_in has one writer -- rows outside a window get zeros without being read -- and the
+ * caller fills nothing.  scratch: cad_pool_head_bwd_scratch_floats(S, B, L, D, mode, half) floats, 8-byte aligned, written before they are
+ * read; needed when dweight or dbias is asked for, and for MAX.  No atomics: the dweight / dbias sums are per-wave registers folded in
+ * wave order, one slot row per workgroup, cad_pool_head_bwd_pieces(L) workgroups per pair, folded by a last launch in an order that
+ * follows from (S, B, L) alone -- run-to-run identical bits, unchanged by a further pair whose g is 0.
+ * MAX additionally takes out (the forward's result) and rows (S, B, D) int64, which cad_pool_head_bwd fills through
+ * cad_pool_head_max_rows before it uses them: rows[s,b,c] = the lowest row whose recomputed y has the bits of out[s,b,c] (the lowest row
+ * with a NaN y where out is NaN) -- torch.max(dim)'s choice on the stored tensor; one more read pass over x (+ residual_in), run from the
+ * backward only.  The y it compares is the forward's bit for bit (same lane map, same code).
+ * cad_pool_head_bwd_supported: the forward's domain; anything else returns CAD_ERR_UNSUPPORTED before a launch. */
+struct cad_pool_head_bwd_args {
+    const void* x;
+    const float* residual_in;
+    const float* weight;
+    const float* bias;
+    const int64_t* centre;
+    const float* g;
+    const float* out; /* MAX only */
+    void* dx;
+    float* dres_in;
+    float* dweight;
+    float* dbias;
+    int64_t* rows; /* MAX only */
+    float* scratch;
+    int64_t B, L, half;
+    int S, D;
+    float eps;
+    int is_rms, x_dtype, y_dtype, mode;
+};
+typedef struct cad_pool_head_bwd_args cad_pool_head_bwd_args;
+int cad_pool_head_bwd(const cad_pool_head_bwd_args* a, void* stream);
+int cad_pool_head_max_rows(const cad_pool_head_bwd_args* a, const float* out, int64_t* rows, float* scratch, void* stream);
+int cad_pool_head_bwd_supported(int D, int x_dtype, int y_dtype, int mode, int64_t half);
+int64_t cad_pool_head_bwd_scratch_floats(int S, int64_t B, int64_t L, int D, int mode, int64_t half);
+int64_t cad_pool_head_bwd_pieces(int64_t L);
+
 /* ---------------------------------------------------------------------------------------------------------
  * hg38 data path -- the step in front of the model.
  *
