@@ -321,8 +321,9 @@ __global__ __launch_bounds__(64 * GP_WAVES, 1) void proj_wx_thin_wgrad_kernel(ca
 // cad_proj_wx's thin kernel (same swizzle, same counted waits).  MFMA roles: A = W fragment (rows = output features), B = X fragment
 // by transposing reads (columns = tokens), so a D lane holds FOUR CONSECUTIVE FEATURES of one token = 8 contiguous bytes of the
 // token-major output; fp32 accumulation over both panels and all of K, one rounding to bf16.
-// The output leaves with ordinary stores: the 8-byte pieces of a token row meet in L2 (streaming stores of partial lines measured 0.277
-// vs 0.212 ms, profiles/r04_out_proj.txt).
+// The output leaves with ordinary stores: the pieces of a token row meet in L2 (streaming stores of 8-byte pieces measured 0.277 vs
+// 0.212 ms, profiles/r04_out_proj.txt; of the 16-byte pieces below: within the noise, profiles/r09_ab_proj_store.txt).  With 32 features
+// per wave (MB = 2) the two accumulator tiles of a token exchange lane rows (cad_d_pair16, cad_stream.h) and leave as 16 bytes per lane.
 #define GP_XTW_RING 4           // LDS tiles of the X ring: RING - 1 chunks (16 KB each) in flight per CU (8 slots measured SLOWER:
                                // 0.222 vs 0.206 ms, profiles/r04_out_proj.txt)
 template <typename TE, int MB, int KS>
@@ -379,7 +380,12 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
     f32x4 d[C::NT / 16][MB];
     int slot = 0;
     int64_t blk = b0;
-    constexpr int NST = (C::NT / 16) * MB;           // output stores per wave and block
+    // The wave's 32 features of a token (MB = 2) are 64 contiguous bytes of the output row: they leave as one 16-byte store per lane
+    // (cad_d_pair16, cad_stream.h) where the rows are 16-byte aligned -- wave-uniform; elsewhere as 8-byte pieces, twice the instructions
+    constexpr bool WIDE = MB == 2;
+    const bool wide = WIDE && (a.ldo % 8) == 0 && (((uintptr_t)out) & 15) == 0;
+    // output stores per wave and block that the counted waits allow for (the 8-byte form issues more: its waits are only stricter)
+    constexpr int NST = (C::NT / 16) * (WIDE ? 1 : MB);
     static_assert(INFL + NST <= 63, "vmcnt is a 6-bit counter");
     int since_store = XR;                             // iterations since the last store burst (wave-uniform)
     for (int64_t bi = 0; bi < nmine; ++bi, blk += bstep) {
@@ -426,6 +432,25 @@ __global__ __launch_bounds__(64 * GP_WAVES, 2) void proj_xTw_kernel(cad_proj_tm_
 #pragma unroll
         for (int q = 0; q < C::NT / 16; ++q) {
             const int64_t t = blk * C::NT + q * 16 + jl;
+            if constexpr (WIDE) {
+                u32x2 pk[2];
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) {
+                    pk[mb][0] = cad_pack2_safe<TE>(d[q][mb][0], d[q][mb][1]);
+                    pk[mb][1] = cad_pack2_safe<TE>(d[q][mb][2], d[q][mb][3]);
+                }
+                if (wide) {  // (wave-uniform; the exchange runs on all lanes, the store under the same mask rules as below)
+                    const u32x4 v = cad_d_pair16(pk[0], pk[1]);
+                    if (t < T && m_wave + 32 <= M) *(u32x4*)((char*)(out + t * a.ldo + m_wave) + cad_d_pair16_off(lane)) = v;
+                } else {
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) {
+                        const int m = m_wave + mb * 16 + g * 4;
+                        if (t < T && m + 4 <= M) *(u32x2*)(out + t * a.ldo + m) = pk[mb];
+                    }
+                }
+                continue;
+            }
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const int m = m_wave + mb * 16 + g * 4;
