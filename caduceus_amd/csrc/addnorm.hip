@@ -4,9 +4,9 @@
 // One wave64 per token row; lane handles channels c = lane + 64*k.  HBM-bound elementwise kernel: every input
 // byte is read once and every output byte written once; statistics stay in registers (wave xor-reduction).
 //
-// cad_rownorm.h holds the wave reduction used here (cad_row_wave_sum) and MIRRORS the forward kernels' per-lane walk for a row held in
-// LDS (decode.hip): a change to the order in which add_norm_fwd_kernel / add_norm_fwd_vec_kernel sum a row, or to where they round,
-// is a change to make there too.
+// The wave reduction, the vector loads and the served type pairs are cad_rownorm.h's.  The two forward kernels below still state the row's
+// statistics and scale themselves (compiled from cad_rownorm.h's routines, some instantiations came out with other bits in a statistic's
+// last place): cad_rownorm.h is where the order they must agree with is written down.
 #include "cad_common.h"
 #include "cad_fp8.h"
 #include "cad_rownorm.h"
@@ -23,11 +23,6 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
     return v;
 }
-// the value a bf16 / fp32 store of `o` leaves in memory (the e4m3 copy is taken from the ROUNDED normed activation, so that it equals
-// cad_quant_rows_fp8 of the stored tensor bit for bit)
-template <typename TY>
-__device__ __forceinline__ float stored_value(float o) { return to_f32(from_f32<TY>(o)); }
-
 template <typename TX, typename TY>
 __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_kernel(cad_add_norm_args a) {
     const int lane = threadIdx.x & 63;
@@ -181,26 +176,6 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_kernel(cad_add_nor
 // the other strand, so they are still one vector store.
 #define ANV_KMAX 4  // D <= 1024
 
-template <typename T>
-__device__ __forceinline__ void ld4(const T* p, float* o);
-template <>
-__device__ __forceinline__ void ld4<float>(const float* p, float* o) {
-    struct __attribute__((aligned(16))) V { float f[4]; };
-    const V t = *(const V*)p;
-    o[0] = t.f[0], o[1] = t.f[1], o[2] = t.f[2], o[3] = t.f[3];
-}
-template <>
-__device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float* o) {
-    struct __attribute__((aligned(8))) V { uint32_t w[2]; };
-    const V t = *(const V*)p;
-    o[0] = cad_bits2f(t.w[0] << 16), o[1] = cad_bits2f(t.w[0] & 0xffff0000u);
-    o[2] = cad_bits2f(t.w[1] << 16), o[3] = cad_bits2f(t.w[1] & 0xffff0000u);
-}
-template <>
-__device__ __forceinline__ void ld4<f16_t>(const f16_t* p, float* o) {
-    cad_ld4_16<f16_t>(p, o);
-}
-
 // KMAX = 256-channel steps per lane: 1 for D <= 256 (a third of the registers of the general instantiation, twice the waves per
 // SIMD), 2 for D <= 512 (configs[4])
 template <typename TX, typename TY, int KMAX, bool FP8 = false>
@@ -223,10 +198,10 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_vec_kernel(cad_add
         for (int k = 0; k < KMAX; ++k) {
             const int c = (lane + 64 * k) * 4;
             if (c < D) {
-                ld4<TX>(x + row * D + c, v[k]);
+                cad_row_ld<TX, 4>(x + row * D + c, v[k]);
                 if (a.residual_in) {
                     float t[4];
-                    ld4<float>(a.residual_in + row * D + c, t);
+                    cad_row_ld<float, 4>(a.residual_in + row * D + c, t);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[k][q] += t[q];
                 }
@@ -266,7 +241,9 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_vec_kernel(cad_add
             a.rstd[row] = rstd;
             if (a.mean) a.mean[row] = mean;
         }
-        float ov[KMAX][4];   // the normed row as it is stored (only read again for the e4m3 copy)
+        // the normed row as it is stored, only read again for the e4m3 copy: taken from the ROUNDED activation, so that it equals
+        // cad_quant_rows_fp8 of the stored tensor bit for bit
+        float ov[KMAX][4];
         float amax = 0.f;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
@@ -274,9 +251,9 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_vec_kernel(cad_add
             if (c < D) {
                 const int oc = a.swap_flip ? (D - 4 - c) : c;  // first of the 4 output channels
                 float w[4], o[4], ro[4];
-                ld4<float>(a.weight + oc, w);
+                cad_row_ld<float, 4>(a.weight + oc, w);
                 float b[4] = {0.f, 0.f, 0.f, 0.f};
-                if (a.bias) ld4<float>(a.bias + oc, b);
+                if (a.bias) cad_row_ld<float, 4>(a.bias + oc, b);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int qi = a.swap_flip ? (3 - q) : q;  // input element feeding output element q
@@ -288,7 +265,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_fwd_vec_kernel(cad_add
                 if (FP8) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        ov[k][q] = stored_value<TY>(o[q]);
+                        ov[k][q] = cad_row_stored<TY>(o[q]);
                         amax = fmaxf(amax, fabsf(ov[k][q]));
                     }
                 }
@@ -334,7 +311,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add
     for (int k = 0; k < KMAX; ++k) {
         const int c = (lane + 64 * k) * 4;
         if (c < D) {
-            ld4<float>(a.weight + (a.swap_flip ? (D - 4 - c) : c), wreg[k]);
+            cad_row_ld<float, 4>(a.weight + (a.swap_flip ? (D - 4 - c) : c), wreg[k]);
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) wreg[k][q] = 0.f;
@@ -357,8 +334,8 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add
             if (c < D) {
                 const int oc = a.swap_flip ? (D - 4 - c) : c;
                 float dyv[4], sm[4];
-                ld4<TY>(dy + orow * D + oc, dyv);
-                ld4<float>(a.sum_saved + orow * D + oc, sm);
+                cad_row_ld<TY, 4>(dy + orow * D + oc, dyv);
+                cad_row_ld<float, 4>(a.sum_saved + orow * D + oc, sm);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     xh[k][q] = (sm[q] - mean) * rstd;
@@ -381,7 +358,7 @@ __global__ __launch_bounds__(64 * AN_WAVES) void add_norm_bwd_vec_kernel(cad_add
             if (c < D) {
                 const int oc = a.swap_flip ? (D - 4 - c) : c;
                 float dro[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
-                if (a.dres_out) ld4<float>(a.dres_out + orow * D + oc, dro);
+                if (a.dres_out) cad_row_ld<float, 4>(a.dres_out + orow * D + oc, dro);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int qo = a.swap_flip ? (3 - q) : q;  // output element that input element q produced
@@ -433,33 +410,23 @@ extern "C" int cad_add_norm_fwd(const cad_add_norm_args* a, void* stream) {
         CAD_CHECK_ARG(a->y_scale != nullptr);
         if (!vec || a->D > 512 || ((uintptr_t)a->y_fp8 % 4) != 0) return CAD_ERR_UNSUPPORTED;
     }
-#define AN_FWD(TX, TY)                                                                  \
-    do {                                                                                \
-        if (vec && a->y_fp8 && a->D <= 256)                                             \
-            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 1, true>), grid, block, 0, stream, *a);  \
-        else if (vec && a->y_fp8)                                                       \
-            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 2, true>), grid, block, 0, stream, *a);  \
-        else if (vec && a->D <= 256)                                                    \
-            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a);  \
-        else if (vec && a->D <= 512)                                                    \
-            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a);  \
-        else if (vec)                                                                   \
-            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a);  \
-        else                                                                            \
-            CAD_LAUNCH((add_norm_fwd_kernel<TX, TY>), grid, block, 0, stream, *a);      \
-    } while (0)
-    if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F32)
-        AN_FWD(float, float);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_BF16)
-        AN_FWD(float, bf16_t);
-    else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
-        AN_FWD(bf16_t, bf16_t);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
-        AN_FWD(float, f16_t);
-    else if (a->x_dtype == CAD_F16 && a->y_dtype == CAD_F16)
-        AN_FWD(f16_t, f16_t);
-    else
-        return CAD_ERR_UNSUPPORTED;
+    const bool served = cad_row_type_pair(a->x_dtype, a->y_dtype, [&](auto tx, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TY = typename decltype(ty)::type;
+        if (vec && a->y_fp8 && a->D <= 256)
+            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 1, true>), grid, block, 0, stream, *a);
+        else if (vec && a->y_fp8)
+            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 2, true>), grid, block, 0, stream, *a);
+        else if (vec && a->D <= 256)
+            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a);
+        else if (vec && a->D <= 512)
+            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a);
+        else if (vec)
+            CAD_LAUNCH((add_norm_fwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a);
+        else
+            CAD_LAUNCH((add_norm_fwd_kernel<TX, TY>), grid, block, 0, stream, *a);
+    });
+    if (!served) return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
 }
 
@@ -487,29 +454,19 @@ static int add_norm_bwd(const cad_add_norm_bwd_args* a, float* wslots, float* bs
     dim3 grid((unsigned)((nrows + per_block - 1) / per_block)), block(64 * AN_WAVES);
     const bool vec = (a->D % 4) == 0 && (((uintptr_t)a->dy | (uintptr_t)a->dres_out | (uintptr_t)a->sum_saved |
                                           (uintptr_t)a->weight | (uintptr_t)a->dx | (uintptr_t)a->dres_in) % 16) == 0;
-#define AN_BWD(TX, TY)                                                                  \
-    do {                                                                                \
-        if (vec && a->D <= 256)                                                         \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
-        else if (vec && a->D <= 512)                                                    \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
-        else if (vec)                                                                   \
-            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);  \
-        else                                                                            \
-            CAD_LAUNCH((add_norm_bwd_kernel<TX, TY>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);      \
-    } while (0)
-    if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F32)
-        AN_BWD(float, float);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_BF16)
-        AN_BWD(float, bf16_t);
-    else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
-        AN_BWD(bf16_t, bf16_t);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
-        AN_BWD(float, f16_t);
-    else if (a->x_dtype == CAD_F16 && a->y_dtype == CAD_F16)
-        AN_BWD(f16_t, f16_t);
-    else
-        return CAD_ERR_UNSUPPORTED;
+    const bool served = cad_row_type_pair(a->x_dtype, a->y_dtype, [&](auto tx, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TY = typename decltype(ty)::type;
+        if (vec && a->D <= 256)
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 1>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);
+        else if (vec && a->D <= 512)
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, 2>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);
+        else if (vec)
+            CAD_LAUNCH((add_norm_bwd_vec_kernel<TX, TY, ANV_KMAX>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);
+        else
+            CAD_LAUNCH((add_norm_bwd_kernel<TX, TY>), grid, block, 0, stream, *a, rows_per_wave, wslots, bslots);
+    });
+    if (!served) return CAD_ERR_UNSUPPORTED;
     return cad_after_launch();
 }
 

@@ -1,7 +1,6 @@
-// What the pool head's forward (pool.hip) and backward (pool_bwd.hip) share: the lane maps and their loads, the normed row (pool_row),
-// the window's span and multiplicities (pool_span_of), torch.max's maximum, the served type pairs and the forward's piece geometry.
-// pool.hip's header describes all of it; nothing here is compiled for one of the two files only, so that the y the backward's MAX
-// search recomputes is the forward's, bit for bit.
+// What the pool head's forward (pool.hip) and backward (pool_bwd.hip) share about pooling: the window's span and multiplicities
+// (pool_span_of), torch.max's maximum, the choice of lane map and the forward's piece geometry.  pool.hip's header describes all of it.
+// The normed row itself -- lane maps, loads, statistics, scale, served type pairs -- is cad_rownorm.h's.
 #pragma once
 #include "cad_common.h"
 #include "cad_rownorm.h"
@@ -34,85 +33,6 @@ inline int64_t pool_rows(int mode, int64_t L, int64_t half) {
     if (mode != CAD_POOL_WINDOW) return L;
     const int64_t n = 2 * half + 1;
     return n < L ? n : L;
-}
-
-// W channels at p -> fp32
-template <typename T, int W>
-__device__ __forceinline__ void pool_ld(const T* p, float* o);
-template <>
-__device__ __forceinline__ void pool_ld<float, 1>(const float* p, float* o) { o[0] = p[0]; }
-template <>
-__device__ __forceinline__ void pool_ld<bf16_t, 1>(const bf16_t* p, float* o) { o[0] = to_f32(p[0]); }
-template <>
-__device__ __forceinline__ void pool_ld<f16_t, 1>(const f16_t* p, float* o) { o[0] = to_f32(p[0]); }
-template <>
-__device__ __forceinline__ void pool_ld<float, 4>(const float* p, float* o) {
-    struct __attribute__((aligned(16))) V { float f[4]; };
-    const V t = *(const V*)p;
-    o[0] = t.f[0], o[1] = t.f[1], o[2] = t.f[2], o[3] = t.f[3];
-}
-template <>
-__device__ __forceinline__ void pool_ld<bf16_t, 4>(const bf16_t* p, float* o) { cad_ld4_16<bf16_t>(p, o); }
-template <>
-__device__ __forceinline__ void pool_ld<f16_t, 4>(const f16_t* p, float* o) { cad_ld4_16<f16_t>(p, o); }
-
-// first channel of lane's step k
-template <int W>
-__device__ __forceinline__ int pool_chan(int lane, int k) { return (lane + 64 * k) * W; }
-
-// v = x + residual of one row, in place -> the normed row as a store in TY leaves it (cad_add_norm_fwd's y, see the header of pool.hip)
-template <typename TY, int W, int KMAX>
-__device__ __forceinline__ void pool_row(float (&v)[KMAX][W], const float (&wreg)[KMAX][W], const float (&breg)[KMAX][W], bool has_bias,
-                                         int D, float eps, int is_rms, int lane) {
-    const float invD = 1.0f / (float)D;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (pool_chan<W>(lane, k) < D) {
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                s1 += v[k][q];
-                s2 += v[k][q] * v[k][q];
-            }
-        }
-    }
-    float mean = 0.f, rstd;
-    if (is_rms) {
-        s2 = cad_row_wave_sum(s2);
-        rstd = cad_rsqrt(s2 * invD + eps);
-    } else {
-        s1 = cad_row_wave_sum(s1);
-        mean = s1 * invD;
-        float qq = 0.f;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            if (pool_chan<W>(lane, k) < D) {
-#pragma unroll
-                for (int q = 0; q < W; ++q) {
-                    const float d = v[k][q] - mean;
-                    qq += d * d;
-                }
-            }
-        }
-        qq = cad_row_wave_sum(qq);
-        rstd = cad_rsqrt(qq * invD + eps);
-    }
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (pool_chan<W>(lane, k) < D) {
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                float o;
-                if (W == 4) {  // the vector kernel adds its bias registers, zeros when there is no bias
-                    o = (v[k][q] - mean) * rstd * wreg[k][q] + breg[k][q];
-                } else {
-                    o = (v[k][q] - mean) * rstd * wreg[k][q];
-                    if (has_bias) o += breg[k][q];
-                }
-                v[k][q] = to_f32(from_f32<TY>(o));
-            }
-        }
-    }
 }
 
 // torch.max's maximum: a NaN on either side stays (v_max_f32 would drop it)
@@ -155,11 +75,6 @@ __device__ __forceinline__ pool_span pool_span_of(int mode, int64_t L, int64_t h
 // the multiplicity of row r of a pair with span w (L == 1: row 0 is also row L - 1 and c_last is 0); rows outside lo .. hi are not asked
 __device__ __forceinline__ float pool_mult(const pool_span& w, int64_t r, int64_t L) {
     return r == 0 ? w.c_first : (r == L - 1 ? w.c_last : 1.f);
-}
-
-inline bool pool_types_ok(int x_dtype, int y_dtype) {  // cad_add_norm_fwd's pairs
-    return (x_dtype == CAD_F32 && (y_dtype == CAD_F32 || y_dtype == CAD_BF16 || y_dtype == CAD_F16)) ||
-           (x_dtype == CAD_BF16 && y_dtype == CAD_BF16) || (x_dtype == CAD_F16 && y_dtype == CAD_F16);
 }
 
 // the lane map a call takes: the vector map where D % 4 == 0 and the row operands are 16-byte aligned

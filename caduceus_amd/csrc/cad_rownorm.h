@@ -1,11 +1,11 @@
-// Add + RMSNorm / LayerNorm of ONE row by one wave64, the row held as fp32 in LDS: the row reduction of addnorm.hip restated for the
-// one-token kernels (decode.hip).  The summation order is cad_add_norm_fwd's at one token: with D % 4 == 0 a lane owns 4 consecutive
-// channels per 256-channel step (add_norm_fwd_vec_kernel, which 16-byte aligned operands take), otherwise channels lane + 64 k
-// (add_norm_fwd_kernel); a lane sums its channels in ascending order, the lanes are combined by the xor butterfly 32, 16, .. 1, and the
-// LayerNorm variance is the second pass over (v - mean).  Same order is not same bits on the device: where the compiler fuses a
-// multiply into an add differs between the two translations, so a statistic may differ in its last bit ("Decode token").
-// addnorm.hip takes cad_row_wave_sum from here; the per-lane walk below is a second statement of its forward kernels' and is kept in
-// step with them by hand (they hold the row in registers and store through their own vector paths).
+// Add + RMSNorm / LayerNorm of ONE row by one wave64: the home of the row -- its lane maps, its loads, its statistics, its
+// scale and where it rounds.  The pool head and its backward (pool.hip, pool_bwd.hip) are compiled from these routines, so the y the
+// backward's MAX search recomputes is the forward's, bit for bit.  Two restatements remain and must be kept in step with this file: the
+// forward kernels of addnorm.hip, which this order is taken from, and cad_row_norm_lds at the end of this file (decode.hip).
+//
+// A lane owns W channels per step of 64 W: W = 4 consecutive channels where D % 4 == 0 and the operands are 16-byte aligned (the vector
+// map), W = 1 otherwise (the scalar map).  A lane sums its channels in ascending order, the lanes are combined by the xor butterfly
+// 32, 16, .. 1, and the LayerNorm variance is the second pass over (v - mean).
 #pragma once
 #include "cad_common.h"
 
@@ -15,11 +15,99 @@ __device__ __forceinline__ float cad_row_wave_sum(float v) {  // every lane rece
     return v;
 }
 
-// channels per lane and step of the row walk
+// channels per lane and step of a row whose operands are aligned
 __device__ __forceinline__ int cad_row_width(int D) { return (D & 3) ? 1 : 4; }
 
-// row[c] (the summed residual stream, fp32) -> row[c] = the normed activation as a store in T leaves it.  All 64 lanes of the wave call
-// this; the caller orders the LDS accesses of other waves around it.
+// first channel of lane's step k
+template <int W>
+__device__ __forceinline__ int cad_row_chan(int lane, int k) { return (lane + 64 * k) * W; }
+
+// W channels of T at p -> fp32
+template <typename T, int W>
+__device__ __forceinline__ void cad_row_ld(const T* p, float* o) {
+    if constexpr (W == 1) {
+        o[0] = to_f32(p[0]);
+    } else if constexpr (sizeof(T) == 4) {
+        struct __attribute__((aligned(16))) V { float f[4]; };
+        const V t = *(const V*)p;
+        o[0] = t.f[0], o[1] = t.f[1], o[2] = t.f[2], o[3] = t.f[3];
+    } else {
+        cad_ld4_16<T>(p, o);
+    }
+}
+
+// mean (0 for RMSNorm) and rstd of the row v = x + residual held in registers (zeros beyond D)
+template <int W, int KMAX>
+__device__ __forceinline__ void cad_row_stats(const float (&v)[KMAX][W], int D, float eps, int is_rms, int lane, float& mean, float& rstd) {
+    const float invD = 1.0f / (float)D;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (cad_row_chan<W>(lane, k) < D) {
+#pragma unroll
+            for (int q = 0; q < W; ++q) {
+                const float t = v[k][q];
+                s1 += t;
+                s2 += t * t;
+            }
+        }
+    }
+    mean = 0.f;
+    if (is_rms) {
+        s2 = cad_row_wave_sum(s2);
+        rstd = cad_rsqrt(s2 * invD + eps);
+    } else {
+        s1 = cad_row_wave_sum(s1);
+        mean = s1 * invD;
+        float qq = 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            if (cad_row_chan<W>(lane, k) < D) {
+#pragma unroll
+                for (int q = 0; q < W; ++q) {
+                    const float d = v[k][q] - mean;
+                    qq += d * d;
+                }
+            }
+        }
+        qq = cad_row_wave_sum(qq);
+        rstd = cad_rsqrt(qq * invD + eps);
+    }
+}
+
+// the normed value before it is rounded.  The vector map adds its bias register, zero when there is no bias; the scalar map adds the
+// bias only when there is one (the compiler may contract the two differently, and -0 + 0 is not -0)
+template <int W>
+__device__ __forceinline__ float cad_row_scale(float v, float mean, float rstd, float w, float b, bool has_bias) {
+    if (W == 4) return (v - mean) * rstd * w + b;
+    float o = (v - mean) * rstd * w;
+    if (has_bias) o += b;
+    return o;
+}
+
+// the value a store of o in T leaves in memory
+template <typename T>
+__device__ __forceinline__ float cad_row_stored(float o) { return to_f32(from_f32<T>(o)); }
+
+// v = x + residual of one row in registers, in place -> the normed row as a store in TY leaves it (cad_add_norm_fwd's y, swap_flip = 0)
+template <typename TY, int W, int KMAX>
+__device__ __forceinline__ void cad_row_norm(float (&v)[KMAX][W], const float (&wreg)[KMAX][W], const float (&breg)[KMAX][W], bool has_bias,
+                                             int D, float eps, int is_rms, int lane) {
+    float mean, rstd;
+    cad_row_stats<W, KMAX>(v, D, eps, is_rms, lane, mean, rstd);
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (cad_row_chan<W>(lane, k) < D) {
+#pragma unroll
+            for (int q = 0; q < W; ++q) v[k][q] = cad_row_stored<TY>(cad_row_scale<W>(v[k][q], mean, rstd, wreg[k][q], breg[k][q], has_bias));
+        }
+    }
+}
+
+// The same for a row held as fp32 in LDS with a run-time D (decode.hip): row[c] (the summed residual stream) -> row[c] = the normed
+// activation as a store in T leaves it.  All 64 lanes of the wave call this; the caller orders the LDS accesses of other waves around it.
+// Stated separately from the routines above, over a run-time W with rolled loops: compiled from them the one-token kernels keep
+// neither their bits nor their registers.  A change to the order above is a change to make here as well.
 template <typename T>
 __device__ __forceinline__ void cad_row_norm_lds(float* row, int D, const float* __restrict__ weight, const float* __restrict__ bias, float eps,
                                                  int is_rms, int lane) {
@@ -64,4 +152,31 @@ __device__ __forceinline__ void cad_row_norm_lds(float* row, int D, const float*
             row[c] = to_f32(from_f32<T>(o));
         }
     }
+}
+
+// ---- host side: the served (x_dtype, y_dtype) pairs, written once ----------------------------------------------------------------
+template <typename T>
+struct cad_type_tag {
+    typedef T type;
+};
+
+// f(cad_type_tag<TX>, cad_type_tag<TY>) for the pair's element types; false, and f not called, where the pair is not served
+template <typename F>
+inline bool cad_row_type_pair(int x_dtype, int y_dtype, F&& f) {
+    if (x_dtype == CAD_F32 && y_dtype == CAD_F32)
+        f(cad_type_tag<float>(), cad_type_tag<float>());
+    else if (x_dtype == CAD_F32 && y_dtype == CAD_BF16)
+        f(cad_type_tag<float>(), cad_type_tag<bf16_t>());
+    else if (x_dtype == CAD_BF16 && y_dtype == CAD_BF16)
+        f(cad_type_tag<bf16_t>(), cad_type_tag<bf16_t>());
+    else if (x_dtype == CAD_F32 && y_dtype == CAD_F16)
+        f(cad_type_tag<float>(), cad_type_tag<f16_t>());
+    else if (x_dtype == CAD_F16 && y_dtype == CAD_F16)
+        f(cad_type_tag<f16_t>(), cad_type_tag<f16_t>());
+    else
+        return false;
+    return true;
+}
+inline bool cad_row_types_ok(int x_dtype, int y_dtype) {
+    return cad_row_type_pair(x_dtype, y_dtype, [](auto, auto) {});
 }

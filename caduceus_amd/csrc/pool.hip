@@ -2,12 +2,8 @@
 // one pass over the pre-norm stream.  Nothing of size L is written: what leaves the kernels is the fixed-order partials in the caller's
 // scratch and out (S, B, D) fp32.
 //
-// A row's normed value y is cad_add_norm_fwd's (csrc/addnorm.hip, swap_flip = 0): the add, the statistics in that kernel's summation order
-// (a lane's channels in ascending order, the xor butterfly of cad_rownorm.h, the two-pass LayerNorm variance), the scale, the rounding to
-// y_dtype.  The lane map is that kernel's too -- 4 consecutive channels per lane and 256-channel step where D % 4 == 0 and the operands
-// are 16-byte aligned (add_norm_fwd_vec_kernel), channels lane + 64 k otherwise (add_norm_fwd_kernel) -- and pool_row (cad_pool.h, shared with
-// the backward in pool_bwd.hip) is a THIRD statement of the per-lane walk next to cad_rownorm.h's: a change to the order in which the
-// forward kernels sum a row, or to where they round, is a change to make there as well (and in pool_bwd.hip's statistics, a fourth).
+// A row's normed value y is cad_add_norm_fwd's (csrc/addnorm.hip, swap_flip = 0): the add, the statistics, the scale, the rounding to
+// y_dtype and the lane map are cad_rownorm.h's (cad_row_norm), which states that kernel's order once for this file and pool_bwd.hip.
 //
 // Geometry.  The rows a (s, b) pair pools -- all L of them for MEAN / MAX, the clamped window's lo .. hi for WINDOW -- are walked from
 // both ends at once: item j is the two rows lo + j and hi - j (one row where they meet), and an item's value is c_a y_a + c_b y_b, two
@@ -48,12 +44,12 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_partial_kernel(cad_pool_
     float wreg[KMAX][W], breg[KMAX][W], acc[KMAX][W];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q) wreg[k][q] = 1.f, breg[k][q] = 0.f, acc[k][q] = is_max ? -INFINITY : 0.f;
         if (c < D && normed) {
-            pool_ld<float, W>(a.weight + c, wreg[k]);
-            if (has_bias) pool_ld<float, W>(a.bias + c, breg[k]);
+            cad_row_ld<float, W>(a.weight + c, wreg[k]);
+            if (has_bias) cad_row_ld<float, W>(a.bias + c, breg[k]);
         }
     }
 
@@ -74,14 +70,14 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_partial_kernel(cad_pool_
                     const int64_t row = e == 0 ? span.lo + j : span.hi - j;
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
-                        const int c = pool_chan<W>(lane, k);
+                        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
                         for (int q = 0; q < W; ++q) v[u][e][k][q] = 0.f;
                         if (c < D) {
-                            pool_ld<TX, W>(x + row * D + c, v[u][e][k]);
+                            cad_row_ld<TX, W>(x + row * D + c, v[u][e][k]);
                             if (res) {
                                 float t[W];
-                                pool_ld<float, W>(res + row * D + c, t);
+                                cad_row_ld<float, W>(res + row * D + c, t);
 #pragma unroll
                                 for (int q = 0; q < W; ++q) v[u][e][k][q] += t[q];
                             }
@@ -97,8 +93,8 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_partial_kernel(cad_pool_
                 const int64_t ra = span.lo + j, rb = span.hi - j;
                 const bool two = ra != rb;  // (the two ends meet on one row where the count is odd: that row is formed twice, used once)
                 if (normed) {
-                    pool_row<TY, W, KMAX>(v[u][0], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
-                    pool_row<TY, W, KMAX>(v[u][1], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
+                    cad_row_norm<TY, W, KMAX>(v[u][0], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
+                    cad_row_norm<TY, W, KMAX>(v[u][1], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
                 }
                 // (L == 1: row 0 is also row L - 1 and c_last is 0)
                 const float ca = ra == 0 ? span.c_first : (ra == a.L - 1 ? span.c_last : 1.f);
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_partial_kernel(cad_pool_
     // the four waves' sums, folded in wave order by the thread that writes the channel
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q)
             if (c + q < D) red[wave][c + q] = acc[k][q];
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(256) void pool_combine_kernel(cad_pool_head_args a,
 }  // namespace
 
 extern "C" int cad_pool_head_supported(int D, int x_dtype, int y_dtype, int mode, int64_t half) {
-    return D >= 1 && D <= POOL_DMAX && pool_types_ok(x_dtype, y_dtype) &&
+    return D >= 1 && D <= POOL_DMAX && cad_row_types_ok(x_dtype, y_dtype) &&
            (mode == CAD_POOL_MEAN || mode == CAD_POOL_MAX || (mode == CAD_POOL_WINDOW && half >= 0 && half < POOL_HALF_MAX));
 }
 
@@ -182,27 +178,19 @@ extern "C" int cad_pool_head(const cad_pool_head_args* a, void* stream) {
     CadProfScope prof(4, stream);
     const bool vec = pool_vec(a->D, a->x, a->residual_in, a->weight, a->bias);
     dim3 grid((unsigned)(sb * g.pieces)), block(64 * POOL_WAVES);
-#define POOL_FWD(TX, TY)                                                                                         \
-    do {                                                                                                         \
-        if (vec && a->D <= 256)                                                                                  \
-            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 1>), grid, block, 0, stream, *a, g.cpp, g.pieces);        \
-        else if (vec && a->D <= 512)                                                                             \
-            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 2>), grid, block, 0, stream, *a, g.cpp, g.pieces);        \
-        else if (vec)                                                                                            \
-            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 4>), grid, block, 0, stream, *a, g.cpp, g.pieces);        \
-        else                                                                                                     \
-            CAD_LAUNCH((pool_partial_kernel<TX, TY, 1, 16>), grid, block, 0, stream, *a, g.cpp, g.pieces);       \
-    } while (0)
-    if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F32)
-        POOL_FWD(float, float);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_BF16)
-        POOL_FWD(float, bf16_t);
-    else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
-        POOL_FWD(bf16_t, bf16_t);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
-        POOL_FWD(float, f16_t);
-    else
-        POOL_FWD(f16_t, f16_t);
+    const bool served = cad_row_type_pair(a->x_dtype, a->y_dtype, [&](auto tx, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TY = typename decltype(ty)::type;
+        if (vec && a->D <= 256)
+            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 1>), grid, block, 0, stream, *a, g.cpp, g.pieces);
+        else if (vec && a->D <= 512)
+            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 2>), grid, block, 0, stream, *a, g.cpp, g.pieces);
+        else if (vec)
+            CAD_LAUNCH((pool_partial_kernel<TX, TY, 4, 4>), grid, block, 0, stream, *a, g.cpp, g.pieces);
+        else
+            CAD_LAUNCH((pool_partial_kernel<TX, TY, 1, 16>), grid, block, 0, stream, *a, g.cpp, g.pieces);
+    });
+    if (!served) return CAD_ERR_UNSUPPORTED;
     const float n = a->mode == CAD_POOL_WINDOW ? (float)(2 * a->half + 1) : (float)a->L;
     const int64_t total = sb * a->D;
     CAD_LAUNCH(pool_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, *a, g.pieces, n);

@@ -4,10 +4,8 @@
 // and cad_add_norm_bwd's sequence turns it into dx / dres_in.  Neither y, dy nor a statistic is ever written; what leaves the kernels
 // besides dx / dres_in is one slot row of dweight / dbias partial sums per workgroup.
 //
-// A row's statistics (pool_row_stats below) are pool_row's (cad_pool.h): its lane maps, its summation order, its two-pass LayerNorm
-// variance.  pool_row is a third statement of cad_add_norm_fwd's per-lane walk (pool.hip's header); this is now a FOURTH: a change to the
-// order in which the forward kernels sum a row is a change to make here as well.  The MAX search does not restate anything: it calls
-// pool_row itself, in the forward's lane map and type pair, so the y it compares with `out` has the forward's bits.
+// A row's statistics are cad_rownorm.h's (cad_row_stats), the routine the pool forward's cad_row_norm is built on; the MAX search calls
+// cad_row_norm itself, in the forward's lane map and type pair, so the y it compares with `out` has the forward's bits.
 //
 // dy.  MEAN / WINDOW: dy[c] = m(r) (g[s,b,c] / n) -- one IEEE division per (s, b, c), formed once per workgroup, and one rounded product
 // with the row's multiplicity m(r) of pool_span_of / pool_mult (an exact integer), not contracted into what follows.  MAX: dy[c] =
@@ -45,44 +43,6 @@ pool_geom pool_bwd_geometry(int64_t L) {
     return g;
 }
 
-// mean and rstd of the row v = x + residual: pool_row's statistics (the fourth statement, see the header of this file)
-template <int W, int KMAX>
-__device__ __forceinline__ void pool_row_stats(const float (&v)[KMAX][W], int D, float eps, int is_rms, int lane, float& mean, float& rstd) {
-    const float invD = 1.0f / (float)D;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (pool_chan<W>(lane, k) < D) {
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                s1 += v[k][q];
-                s2 += v[k][q] * v[k][q];
-            }
-        }
-    }
-    mean = 0.f;
-    if (is_rms) {
-        s2 = cad_row_wave_sum(s2);
-        rstd = cad_rsqrt(s2 * invD + eps);
-    } else {
-        s1 = cad_row_wave_sum(s1);
-        mean = s1 * invD;
-        float qq = 0.f;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            if (pool_chan<W>(lane, k) < D) {
-#pragma unroll
-                for (int q = 0; q < W; ++q) {
-                    const float d = v[k][q] - mean;
-                    qq += d * d;
-                }
-            }
-        }
-        qq = cad_row_wave_sum(qq);
-        rstd = cad_rsqrt(qq * invD + eps);
-    }
-}
-
 // dy of a MEAN / WINDOW row: one rounded product (not contracted into the sums it feeds)
 __device__ __forceinline__ float pool_dy(float m, float gd) {
 #pragma clang fp contract(off)
@@ -95,14 +55,14 @@ template <typename TX, int W, int KMAX>
 __device__ __forceinline__ void pool_load_row(float (&v)[KMAX][W], const TX* x, const float* res, int64_t row, int D, int lane) {
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q) v[k][q] = 0.f;
         if (c < D) {
-            pool_ld<TX, W>(x + row * D + c, v[k]);
+            cad_row_ld<TX, W>(x + row * D + c, v[k]);
             if (res) {
                 float t[W];
-                pool_ld<float, W>(res + row * D + c, t);
+                cad_row_ld<float, W>(res + row * D + c, t);
 #pragma unroll
                 for (int q = 0; q < W; ++q) v[k][q] += t[q];
             }
@@ -152,11 +112,11 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(cad_pool_head
     int64_t sel[KMAX][W];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q) wreg[k][q] = 1.f, gd[k][q] = 0.f, dw[k][q] = 0.f, db[k][q] = 0.f, sel[k][q] = -1;
         if (c < D) {
-            if (normed) pool_ld<float, W>(a.weight + c, wreg[k]);
+            if (normed) cad_row_ld<float, W>(a.weight + c, wreg[k]);
 #pragma unroll
             for (int q = 0; q < W; ++q) {
                 const float gv = a.g[sb * D + c + q];
@@ -193,14 +153,14 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(cad_pool_head
             float mean = 0.f, rstd = 1.f, sg = 0.f, sgx = 0.f;
             float gw[KMAX][W];
             if (normed) {
-                pool_row_stats<W, KMAX>(v[u], D, a.eps, NORM == POOL_NORM_RMS, lane, mean, rstd);
+                cad_row_stats<W, KMAX>(v[u], D, a.eps, NORM == POOL_NORM_RMS, lane, mean, rstd);
                 mean = inside ? mean : 0.f, rstd = inside ? rstd : 0.f;  // a row of zeros stays one (eps may be 0)
             }
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
 #pragma unroll
                 for (int q = 0; q < W; ++q) gw[k][q] = 0.f;
-                if (pool_chan<W>(lane, k) < D) {
+                if (cad_row_chan<W>(lane, k) < D) {
 #pragma unroll
                     for (int q = 0; q < W; ++q) {
                         const float dy = is_max ? (sel[k][q] == r ? gd[k][q] : 0.f) : pool_dy(m, gd[k][q]);
@@ -236,7 +196,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(cad_pool_head
             if (r < a.L) {  // wave-uniform
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) {
-                    const int c = pool_chan<W>(lane, k);
+                    const int c = cad_row_chan<W>(lane, k);
                     if (c < D) pool_store_row<TX, W>(dx, dri, r * D + c, v[u][k]);
                 }
             }
@@ -249,7 +209,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_bwd_kernel(cad_pool_head
         float* slots = pass == 0 ? wslots : bslots;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
-            const int c = pool_chan<W>(lane, k);
+            const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
             for (int q = 0; q < W; ++q)
                 if (c + q < D) red[wave][c + q] = pass == 0 ? dw[k][q] : db[k][q];
@@ -289,7 +249,7 @@ __global__ __launch_bounds__(POOL_FOLD_CH * POOL_FOLD_SUB) void pool_bwd_fold_ke
 #define POOL_NO_ROW INT64_MAX
 
 // Per (pair, piece) and channel: the lowest row of the piece whose y has the bits of out (is NaN where out is NaN), POOL_NO_ROW if none.
-// The forward's lane map, type pair and pool_row, so that y is the forward's; the rows in the backward's geometry (a minimum does not
+// The forward's lane map, type pair and cad_row_norm, so that y is the forward's; the rows in the backward's geometry (a minimum does not
 // depend on the walk).
 template <typename TX, typename TY, int W, int KMAX>
 __global__ __launch_bounds__(64 * POOL_WAVES) void pool_max_rows_kernel(cad_pool_head_bwd_args a, const float* out, int64_t* part, int64_t cpp,
@@ -309,13 +269,13 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_max_rows_kernel(cad_pool
     int64_t best[KMAX][W];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q) wreg[k][q] = 1.f, breg[k][q] = 0.f, want[k][q] = 0.f, best[k][q] = POOL_NO_ROW;
         if (c < D) {
             if (normed) {
-                pool_ld<float, W>(a.weight + c, wreg[k]);
-                if (has_bias) pool_ld<float, W>(a.bias + c, breg[k]);
+                cad_row_ld<float, W>(a.weight + c, wreg[k]);
+                if (has_bias) cad_row_ld<float, W>(a.bias + c, breg[k]);
             }
 #pragma unroll
             for (int q = 0; q < W; ++q) want[k][q] = out[sb * D + c + q];
@@ -336,7 +296,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_max_rows_kernel(cad_pool
         for (int u = 0; u < POOL_BWD_ROWS; ++u) {
             const int64_t r = base + u * POOL_WAVES;
             if (r >= a.L) continue;  // wave-uniform
-            if (normed) pool_row<TY, W, KMAX>(v[u], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
+            if (normed) cad_row_norm<TY, W, KMAX>(v[u], wreg, breg, has_bias, D, a.eps, a.is_rms, lane);
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
 #pragma unroll
@@ -350,7 +310,7 @@ __global__ __launch_bounds__(64 * POOL_WAVES) void pool_max_rows_kernel(cad_pool
 
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const int c = pool_chan<W>(lane, k);
+        const int c = cad_row_chan<W>(lane, k);
 #pragma unroll
         for (int q = 0; q < W; ++q)
             if (c + q < D) red[wave][c + q] = best[k][q];
@@ -408,27 +368,19 @@ extern "C" int cad_pool_head_max_rows(const cad_pool_head_bwd_args* a, const flo
     int64_t* part = (int64_t*)scratch;
     const bool vec = pool_vec(a->D, a->x, a->residual_in, a->weight, a->bias);  // the forward's choice
     dim3 grid((unsigned)(sb * g.pieces)), block(64 * POOL_WAVES);
-#define POOL_ROWS(TX, TY)                                                                                              \
-    do {                                                                                                               \
-        if (vec && a->D <= 256)                                                                                        \
-            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 1>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);  \
-        else if (vec && a->D <= 512)                                                                                   \
-            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 2>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);  \
-        else if (vec)                                                                                                  \
-            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 4>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);  \
-        else                                                                                                           \
-            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 1, 16>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces); \
-    } while (0)
-    if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F32)
-        POOL_ROWS(float, float);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_BF16)
-        POOL_ROWS(float, bf16_t);
-    else if (a->x_dtype == CAD_BF16 && a->y_dtype == CAD_BF16)
-        POOL_ROWS(bf16_t, bf16_t);
-    else if (a->x_dtype == CAD_F32 && a->y_dtype == CAD_F16)
-        POOL_ROWS(float, f16_t);
-    else
-        POOL_ROWS(f16_t, f16_t);
+    const bool served = cad_row_type_pair(a->x_dtype, a->y_dtype, [&](auto tx, auto ty) {
+        using TX = typename decltype(tx)::type;
+        using TY = typename decltype(ty)::type;
+        if (vec && a->D <= 256)
+            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 1>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);
+        else if (vec && a->D <= 512)
+            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 2>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);
+        else if (vec)
+            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 4, 4>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);
+        else
+            CAD_LAUNCH((pool_max_rows_kernel<TX, TY, 1, 16>), grid, block, 0, stream, *a, out, part, g.cpp, g.pieces);
+    });
+    if (!served) return CAD_ERR_UNSUPPORTED;
     const int64_t total = sb * a->D;
     CAD_LAUNCH(pool_max_rows_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, part, rows, total, g.pieces, a->D);
     return cad_after_launch();

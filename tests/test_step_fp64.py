@@ -48,7 +48,7 @@ Launch 3 (step_out_kernel), from the device's y: the dot bound of launch 1 with 
 Decode token (generation.DecodeStack, one step on a cache the test fills with drawn values, so that every window column and state lane
 is non-zero and the full-sequence kernels' own shape limits do not restrict the geometry):
   residual  layer 0: equals emb[id] bit for bit; later layers: t = out + res, one fp32 add: u |t| (an_reference's res_out).
-  xz        fp64 add+norm by an_reference (y, tol_y; the row statistics in cad_add_norm_fwd's order, which cad_row_norm_lds restates),
+  xz        fp64 add+norm by an_reference (y, tol_y; the row statistics in cad_add_norm_fwd's order, which cad_row_norm_lds of csrc/cad_rownorm.h restates),
             through the W_in dot: e = sum |W| tol_y + g(D + 8) sum |W| (|y| + tol_y) + D UF, then the roundings of launch 1.
   xc, ssm_state, y, out   as above, from the device's conv_state / xc, z / y.
   logits    final add+norm of the device's out + res (an_reference), through the head dot with the same carry; fp32 output.
