@@ -15,11 +15,13 @@ from .generation import InferenceParams, decode_step, generate
 from .scoring import masked_logprobs, sequence_logprobs, variant_llr
 from .infilling import infill
 from .embedding import pooled_embeddings
+from .attribution import MaskedTarget, attribute
 
 __all__ = ["DNAEmbeddingModelCaduceus", "SequenceDecoder", "CaduceusConfig", "Caduceus", "CaduceusForMaskedLM", "CaduceusForSequenceClassification",
            "CaduceusTokenizer", "CaduceusMixerModel", "BiMambaWrapper", "create_block", "RCPSEmbedding", "RCPSWrapper",
            "RCPSAddNormWrapper", "RCPSMambaBlock", "RCPSLMHead", "fp16_kernels", "register_auto_classes", "InferenceParams",
-           "decode_step", "generate", "sequence_logprobs", "masked_logprobs", "variant_llr", "infill", "pooled_embeddings"]
+           "decode_step", "generate", "sequence_logprobs", "masked_logprobs", "variant_llr", "infill", "pooled_embeddings",
+           "attribute", "MaskedTarget"]
 
 
 def register_auto_classes():

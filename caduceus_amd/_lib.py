@@ -166,6 +166,11 @@ class LmScoreArgs(C.Structure):
                 ("dtype", _i)]
 
 
+class EmbedAttribArgs(C.Structure):
+    _fields_ = [("dh", _p), ("weight", _p), ("comp", _p), ("ids", _p), ("allowed", _p), ("grad", _p), ("gxi", _p), ("rows", _i64),
+                ("D", _i), ("V", _i), ("n_strands", _i), ("A", _i), ("centre", _i), ("dtype", _i)]
+
+
 class LmUnmaskArgs(C.Structure):
     _fields_ = [("hidden", _p), ("weight", _p), ("comp", _p), ("ids_in", _p), ("ids_out", _p), ("conf", _p), ("u_out", _p),
                 ("sampler", SamplerArgs), ("rows", _i64), ("L", _i64), ("D", _i), ("V", _i), ("n_strands", _i), ("mask_id", _i64),
@@ -258,6 +263,8 @@ SYMBOLS = {
     "cad_lm_head_bwd_partials": (_i64, [_i64]),
     "cad_lm_head_score": (_i, [C.POINTER(LmScoreArgs), _p]),
     "cad_lm_head_score_supported": (_i, [_i, _i, _i]),
+    "cad_embed_attrib": (_i, [C.POINTER(EmbedAttribArgs), _p]),
+    "cad_embed_attrib_supported": (_i, [_i, _i, _i]),
     "cad_lm_head_unmask": (_i, [C.POINTER(LmUnmaskArgs), _p]),
     "cad_lm_head_unmask_supported": (_i, [_i, _i, _i]),
     "cad_pool_head": (_i, [C.POINTER(PoolHeadArgs), _p]),

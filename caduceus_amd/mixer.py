@@ -21,8 +21,10 @@ Scan launches with fewer workgroups than the GPU has CUs are L-split (ops.lsplit
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
 from collections import namedtuple
 
 import torch
@@ -198,6 +200,27 @@ _STREAM_FOLD_MIN_CHUNKS = 16  # rows shorter than this many 512-position chunks 
 # test hook (tests/test_configs.py): a list here receives, per backward call, the operands of the x_proj weight gradient of both
 # parameter sets as the kernels saw them -- {"ddbc": [d(dt_lr ; B ; C) (R + 2N, T)] * 2, "xc": [conv output (E, T)] * 2} (clones)
 CAPTURE_XPROJ_OPERANDS = None
+
+
+_grad_scope = threading.local()
+
+
+@contextlib.contextmanager
+def input_grad_only(enabled: bool = True):
+    """While active (thread-local), a BiMambaMixerFn forward records that its backward owes only d(x2d): the gradient of the layer's
+    input, for attributions (caduceus_amd.attribution) -- no weight-gradient product, no slot sums, no fold launch, no parameter casts;
+    every parameter receives None.  It is the forward that decides: parameters normally require grad, so ctx.needs_input_grad cannot.
+    The kernels that produce small parameter sums as a by-product (scan dA / dD / dbias, conv dw) run as they are; their sums are dropped."""
+    prev = getattr(_grad_scope, "input_only", False)
+    _grad_scope.input_only = bool(enabled)
+    try:
+        yield
+    finally:
+        _grad_scope.input_only = prev
+
+
+def input_grad_only_enabled() -> bool:
+    return bool(getattr(_grad_scope, "input_only", False))
 
 
 def set_fp8_in_proj(on: bool) -> None:
@@ -484,12 +507,13 @@ def _scan_bwd(sets, xz, ycat, dy, seg_P, meta):
     return dxz, work, ddbcs, [(zero["conv_dw", i], zero["conv_db", i] if s.conv_b is not None else None) for i, s in enumerate(sets)]
 
 
-def _d_dt_lr(s, w, ddbc, i, cache, slots):
+def _d_dt_lr(s, w, ddbc, i, cache, slots, want_dW=True):
     """d(dt_lr) = W_dt^T d(delta) into rows [:R] of d(dbc) (rows [R:] hold the folded dB / dC: the gradient of [dt_lr ; B ; C] is
-    assembled in place), and dW_dt (E, R) fp32 -- or None: left in slots["dt"][i] for the fold of the weight-gradient partials."""
+    assembled in place), and dW_dt (E, R) fp32 -- or None: left in slots["dt"][i] for the fold of the weight-gradient partials.
+    want_dW=False (input_grad_only): the plain product alone, and None."""
     (E, T), R = s.xc.shape, s.w_dt.shape[1]
     ddelta, dt_lr, out = w.ddelta, s.dbc[:R], ddbc[:R]
-    if _FUSED_WGRAD and ops.proj_wx_wgrad_supported(ddelta, R, E, T):
+    if want_dW and _FUSED_WGRAD and ops.proj_wx_wgrad_supported(ddelta, R, E, T):
         # d(dt_lr) and dW_dt = d(delta) dt_lr^T from ONE pass over d(delta) (cad_proj_wx_wgrad)
         if "dt" not in slots:
             slots["dt"] = ops.wgrad_partials(T, E, R, ddelta.device, nsets=2)
@@ -499,6 +523,8 @@ def _d_dt_lr(s, w, ddbc, i, cache, slots):
         ops.proj_wx(_transposed(cache, "w_dtT", s.w_dt, i), ddelta, out=out)
     else:
         ops.mm(s.w_dt.t(), ddelta, out=out)
+    if not want_dW:
+        return None
     if _OWN_DWX and _own_wgrad_chunked_ok(ddelta, R):
         return _own_wgrad_chunked(ddelta, dt_lr).t()
     return _wgrad_cm_cm(ddelta, dt_lr)
@@ -564,6 +590,20 @@ def _wgrad_slot_sums(slots, glue):
     return sums
 
 
+def _backward_input_only(dout2d, xz, w_in, w_out, ycat, sets, seg_P, meta, cache):
+    """d(x2d) alone (input_grad_only): the stages d(x2d) depends on, in the full backward's order -- d(y), the scan backward with its
+    dB / dC fold, d(dt_lr), d(xc), the conv backward, d(x2d).  No weight-gradient product, slot, slot sum or fold launch."""
+    E = xz.shape[0] // 2
+    T = dout2d.shape[0]
+    dy = _d_y(dout2d, w_out, cache)
+    dxz, work, ddbcs, conv_bufs = _scan_bwd(sets, xz, ycat, dy, seg_P, meta)
+    for i, (s, w, ddbc) in enumerate(zip(sets, work, ddbcs)):
+        _d_dt_lr(s, w, ddbc, i, cache, None, want_dW=False)
+        _d_xc(s, w.du, ddbc, i, cache)
+    _conv_bwd2(xz[:E], [(s.conv_w, s.conv_b) for s in sets], [w.du for w in work], dxz[:E], meta.split, _DIRS, bufs=conv_bufs)
+    return _d_x2d(dxz.view(2 * E, T), w_in, cache)
+
+
 class BiMambaMixerFn(torch.autograd.Function):
     """out (T, D) = out_proj(scan_f + scan_r) for normed input x2d (T, D), T = S*B*L rows in t-frame order.
 
@@ -599,6 +639,7 @@ class BiMambaMixerFn(torch.autograd.Function):
         sets, seg_P = _scan_fwd(sets, z, ycat, delta_is_dt, split, k)
         out2d = _out_proj(w_out, ycat.view(2 * E, T), cache)
         ctx.cache = cache  # (not saved tensors: plain per-step copies owned by the cache)
+        ctx.input_grad_only = input_grad_only_enabled()
         ctx.save_for_backward(x2d, xz, w_in, w_out, ycat, *_flatten(sets), *seg_P)
         ctx.meta = Meta(SB, Lq, split, [SetParams(*(None if t is None else t.dtype for t in p)) for p in params],
                         [p.conv_w.shape for p in params], W_in.dtype, W_out.dtype, tuple(delta_is_dt), k)
@@ -612,6 +653,8 @@ class BiMambaMixerFn(torch.autograd.Function):
         T = x2d.shape[0]
         E = xz.shape[0] // 2
         dout2d = dout2d.contiguous()
+        if ctx.input_grad_only:
+            return (_backward_input_only(dout2d, xz, w_in, w_out, ycat, sets, seg_P, meta, cache),) + (None,) * (7 + 2 * len(SetParams._fields))
         glue = []  # (src, dst, n, nparts, stride, nparts2, stride2) jobs of the one fp32 fold launch at the end (_GLUE_FOLD)
         slots = {}  # "dt" / "x": fp32 partial slots of the own weight-gradient kernels, both sets (allocated by the first set that uses them)
         dy = _d_y(dout2d, w_out, cache)

@@ -138,10 +138,17 @@ class CaduceusMixerModel(nn.Module):
                                                                     **factory_kwargs)
         self.norm_f = norm_f if (config.fused_add_norm or not config.rcps) else RCPSAddNormWrapper(norm_f)
 
-    def layers_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None):
+    def layers_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None, hidden0: Optional[torch.Tensor] = None):
         """Embedding and layer loop without the final norm: (hidden (S, B, L, D), fp32 residual stream | None, compute dtype) -- the
-        operands of the final add + norm, which forward_tframe writes out and forward_tframe_pooled pools without writing."""
-        if inputs_embeds is not None:
+        operands of the final add + norm, which forward_tframe writes out and forward_tframe_pooled pools without writing.
+        hidden0: an already-embedded t-frame tensor (S, B, L, D) (embeddings.forward_tframe's output, or a point on a path from it) in
+        place of input_ids / inputs_embeds: it enters the first layer as it is -- no frame conversion, no re-embedding."""
+        if hidden0 is not None:
+            if hidden0.dim() != 4 or hidden0.shape[0] != (2 if self.rcps else 1):
+                raise ValueError(f"hidden0 is ({2 if self.rcps else 1}, B, L, D) in the t-frame, got {tuple(hidden0.shape)}")
+            act = act_dtype_of(hidden0)
+            hidden = hidden0 if hidden0.dtype in (torch.float32, act) else hidden0.to(act)
+        elif inputs_embeds is not None:
             act = act_dtype_of(inputs_embeds)
             hidden = engine.to_tframe(inputs_embeds, self.rcps)
             if hidden.dtype not in (torch.float32, act):
@@ -169,9 +176,10 @@ class CaduceusMixerModel(nn.Module):
         nf = self.norm_f.submodule if isinstance(self.norm_f, RCPSAddNormWrapper) else self.norm_f
         return norm_params(nf)
 
-    def forward_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None) -> torch.Tensor:
+    def forward_tframe(self, input_ids, inputs_embeds=None, collect: Optional[list] = None,
+                       hidden0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns the final normed hidden state in the t-frame (S, B, L, D) in the compute dtype."""
-        hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds, collect)
+        hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds, collect, **({} if hidden0 is None else {"hidden0": hidden0}))
         w, b, eps, is_rms = self._final_norm_params()
         # final norm never swaps strands (modeling_caduceus.py:234-262)
         hidden, _ = ops.add_norm(hidden, residual, w, b, eps, is_rms, False, act)
@@ -180,13 +188,13 @@ class CaduceusMixerModel(nn.Module):
         return hidden
 
     def forward_tframe_pooled(self, input_ids, inputs_embeds=None, mode: str = "mean", centre: Optional[torch.Tensor] = None,
-                              half: int = 0, grad: bool = False) -> torch.Tensor:
+                              half: int = 0, grad: bool = False, hidden0: Optional[torch.Tensor] = None) -> torch.Tensor:
         """forward_tframe followed by pooling over the sequence, as ONE pass over the last layer's output (ops.pool_head): the final
         normed (S, B, L, D) activation is never written.  mode "mean" / "max" / "window" (centre (S, B) int64 t-frame positions, offsets
         -half .. half, clamped).  Returns (S, B, D) fp32.  By default it runs under torch.no_grad(); grad=True follows the ambient grad
         mode and pools through ops.pool_head_grad, whose backward recomputes the rows instead of saving them."""
         with contextlib.nullcontext() if grad else torch.no_grad():
-            hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds)
+            hidden, residual, act = self.layers_tframe(input_ids, inputs_embeds, **({} if hidden0 is None else {"hidden0": hidden0}))
             w, b, eps, is_rms = self._final_norm_params()
             head = ops.pool_head_grad if grad else ops.pool_head
             return head(hidden, residual, w, b, eps, is_rms, act, mode, centre, half)
@@ -494,6 +502,36 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
         mode, centre, half = tframe_pooling(self.pooling_strategy, 2 if backbone.rcps else 1, like.shape[0], like.shape[1], like.device)
         return backbone.forward_tframe_pooled(input_ids, inputs_embeds, mode, centre, half, grad=self.fused_pool_train)
 
+    def _score_pooled(self, pooled):
+        """Class logits of one or two pooled (B, D) embeddings: two are scored apart and averaged (RCPS strands, conjoined inputs)."""
+        wdt = self.score.weight.dtype
+        logits = self.score(pooled[0].to(wdt))
+        if len(pooled) == 2:
+            logits = (logits + self.score(pooled[1].to(wdt))) / 2
+        return logits
+
+    def conjoins(self) -> bool:
+        """Post-hoc conjoining is in force: input_ids is (B, L, 2) and its two channels run as one batch of 2 B rows."""
+        return (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
+
+    def logits_from_hidden0(self, hidden0: torch.Tensor) -> torch.Tensor:
+        """forward()'s class logits from an already-embedded t-frame input hidden0 (S, B, L, D) (CaduceusMixerModel.layers_tframe),
+        through the model's own pooling, pool head and conjoin settings; with conjoining, rows [B / 2:] are the second channel."""
+        backbone = self.caduceus.backbone
+        S, B, Lq = hidden0.shape[:3]
+        if self.fused_pool_train or (self.fused_pool and not torch.is_grad_enabled()):
+            from .embedding import tframe_pooling
+            mode, centre, half = tframe_pooling(self.pooling_strategy, S, B, Lq, hidden0.device)
+            pooled = list(backbone.forward_tframe_pooled(None, None, mode, centre, half, grad=self.fused_pool_train, hidden0=hidden0))
+        else:
+            t = backbone.forward_tframe(None, None, None, hidden0=hidden0)
+            pooled = [self.pool_hidden_states(t[0])]
+            if S == 2:
+                pooled.append(self.pool_hidden_states(t[1], reversed_positions=True))
+        if self.conjoins():
+            pooled = [pooled[0][:B // 2], pooled[0][B // 2:]]
+        return self._score_pooled(pooled)
+
     def _sequence_loss(self, logits, labels):
         """HF convention (config.problem_type, inferred once from the label dtype / num_labels when unset)."""
         labels = labels.to(logits.device)
@@ -520,7 +558,7 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
             return_dict = return_dict if return_dict is not None else self._return_dict_default
             backbone = self.caduceus.backbone
             collect = [] if output_hidden_states else None
-            conjoin = (not self.config.rcps) and (self.conjoin_train or (self.conjoin_eval and not self.training))
+            conjoin = self.conjoins()
             fused = (self.fused_pool_train or (self.fused_pool and not torch.is_grad_enabled())) and collect is None
             if conjoin:
                 if input_ids is None:
@@ -544,10 +582,7 @@ class CaduceusForSequenceClassification(CaduceusPreTrainedModel):
                 pooled = [self.pool_hidden_states(t[0])]
                 if self.config.rcps:  # second strand: positions run the other way in the reference's stacked frame
                     pooled.append(self.pool_hidden_states(t[1], reversed_positions=True))
-            wdt = self.score.weight.dtype
-            logits = self.score(pooled[0].to(wdt))
-            if len(pooled) == 2:
-                logits = (logits + self.score(pooled[1].to(wdt))) / 2
+            logits = self._score_pooled(pooled)
             loss = self._sequence_loss(logits, labels) if labels is not None else None
             hidden = tuple(as_requested(engine.from_tframe(h), logits) for h in collect) if collect is not None else None
             if not return_dict:

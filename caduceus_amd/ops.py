@@ -772,6 +772,65 @@ def lm_head_score(hidden_t: torch.Tensor, weight: torch.Tensor, comp: Optional[t
     return (logp, logp_all) if want_all else logp
 
 
+class AttribUnsupported(ValueError):
+    """The embedding lies outside what cad_embed_attrib serves (vocab_size <= 16 on an fp32 / bf16 / fp16 gradient)."""
+
+
+def embed_attrib_supported(D: int, V: int, act: torch.dtype) -> bool:
+    if act not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    return bool(L.get_lib().cad_embed_attrib_supported(int(D), int(V), L.dtype_code(act)))
+
+
+def embed_attrib(dh_t: torch.Tensor, weight: torch.Tensor, comp: Optional[torch.Tensor], ids: torch.Tensor, allowed: torch.Tensor,
+                 centre: bool = True, want_grad: bool = True, want_gxi: bool = True):
+    """Nucleotide attributions from the gradient dh_t (S, ..., D) of a score w.r.t. the t-frame embedding output, in one launch
+    (cad_embed_attrib): g[v] = <dh0, E[v]> + <dh1, E[comp v]> is the gradient w.r.t. the one-hot input, the LM head's logit row with the
+    embedding table `weight` (V, D) as the weight.  allowed: int64, ascending and unique, A ids in [0, V).  centre: the mean of g over
+    the allowed ids is subtracted.  want_grad -> grad (..., A) fp32, columns in the order of `allowed`; want_gxi -> gxi (...) fp32, the
+    (centred) value at the row's own id `ids`, exactly 0.0 where that id is not allowed.  Returns grad, gxi, or (grad, gxi).
+    No autograd: the inputs are detached.  An embedding the kernel does not serve raises AttribUnsupported."""
+    if not (want_grad or want_gxi):
+        raise ValueError("embed_attrib: ask for grad, gxi, or both")
+    S, D = dh_t.shape[0], dh_t.shape[-1]
+    V = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != D:
+        raise ValueError(f"embed_attrib: weight must be (V, {D}), got {tuple(weight.shape)}")
+    if not embed_attrib_supported(D, V, dh_t.dtype):
+        raise AttribUnsupported(f"embed_attrib: cad_embed_attrib does not serve d_model {D}, vocab_size {V} in {dh_t.dtype} "
+                                "(vocab_size <= 16; float32, bfloat16 or float16 gradient)")
+    if S not in (1, 2) or (S == 2 and comp is None):
+        raise ValueError("embed_attrib: dh is (1, ..., D), or (2, ..., D) with a complement map")
+    dh = dh_t.detach().contiguous()
+    shape = tuple(dh.shape[1:-1])
+    rows = math.prod(shape)
+    if rows == 0:
+        raise ValueError("embed_attrib: nothing to attribute")
+    if ids.dtype != torch.int64 or ids.numel() != rows:
+        raise TypeError(f"embed_attrib: ids holds {rows} int64 values, one per row")
+    if allowed.dtype != torch.int64 or allowed.dim() != 1 or not 1 <= allowed.numel() <= V:
+        raise TypeError(f"embed_attrib: allowed holds 1 .. {V} int64 ids")
+    if allowed.device.type == "cpu":  # what the host holds is checked on the host
+        al = allowed.tolist()
+        if al != sorted(set(al)) or al[0] < 0 or al[-1] >= V:
+            raise ValueError(f"embed_attrib: allowed must be ascending, unique and lie in [0, {V})")
+    A = allowed.numel()
+    w = weight.detach().float().contiguous()
+    ids = ids.reshape(-1).contiguous()
+    allowed = allowed.contiguous()
+    dev = dh.device
+    grad = torch.empty(shape + (A,), dtype=torch.float32, device=dev) if want_grad else None
+    gxi = torch.empty(shape, dtype=torch.float32, device=dev) if want_gxi else None
+    cmap = comp if S == 2 else None
+    stream = L.stream_and_check(dh, w, cmap, ids, allowed, grad, gxi)
+    a = L.EmbedAttribArgs(L.ptr(dh), L.ptr(w), L.ptr(cmap), L.ptr(ids), L.ptr(allowed), L.ptr(grad), L.ptr(gxi), rows, D, V, S, A,
+                          int(bool(centre)), L.dtype_code(dh.dtype))
+    L.check(L.get_lib().cad_embed_attrib(C.byref(a), stream), "cad_embed_attrib")
+    if grad is None:
+        return gxi
+    return (grad, gxi) if want_gxi else grad
+
+
 def lm_head_unmask_supported(D: int, V: int, act: torch.dtype) -> bool:
     if act not in (torch.float32, torch.bfloat16, torch.float16):
         return False

@@ -784,6 +784,38 @@ typedef struct cad_lm_score_args cad_lm_score_args;
 int cad_lm_head_score(const cad_lm_score_args* a, void* stream);
 int cad_lm_head_score_supported(int D, int V, int dtype);
 
+/* Attribution head: the gradient of a score with respect to the one-hot input sequence, straight from the gradient of the t-frame
+ * embedding output, in one launch.  For ids x the embedding output is h0[b,l] = E[x], h1[b,l] = E[comp x], hence
+ *   g[i][v]  = d score / d onehot[i][v] = <dh0[i], E[v]> + <dh1[i], E[comp v]>: the logit row cad_lm_head_fwd forms, with dh as the hidden
+ *              state and the embedding table as the weight (fp32 accumulation, each strand's sum kept apart, then one commutative add:
+ *              exchanging the two strands of dh gives the same numbers at columns comp v, bit for bit)
+ *   m[i]     = centre ? (sum of g[i][v] over the allowed ids, in ascending id order) / A : 0
+ *   grad[i][k] = g[i][allowed[k]] - m[i]
+ *   gxi[i]   = g[i][ids[i]] - m[i] where ids[i] is an allowed id; exactly 0.0f elsewhere (N, pad, mask, ids outside [0, V))
+ * dh: (S, rows, D) F32 / BF16 / F16.  weight: (V, D) fp32, the embedding table.  comp: S == 2 only.  ids: (rows) int64, needed with gxi.
+ * allowed: (A) int64, ascending and unique, 1 <= A <= V; entries outside [0, V) are dropped.  grad (rows, A) and gxi (rows) fp32: at
+ * least one is given, an output that is NULL is neither computed nor written.  Neither a (rows, V) tensor nor a reference-frame
+ * (B, L, 2 D) gradient is written.
+ * One launch on `stream`, no allocation, no synchronisation, no atomics, no shared memory: every output element has one writer, and a
+ * row's result does not depend on the rows around it.  cad_embed_attrib_supported: what cad_lm_head_score_supported serves (any D >= 1,
+ * 1 <= V <= 16, the three dtypes); anything else returns CAD_ERR_UNSUPPORTED before a launch.  D 128 / 256 (512 in bf16) with a
+ * 16-byte aligned dh run on the matrix cores on tiles of 16 consecutive rows, everything else one wave per row. */
+struct cad_embed_attrib_args {
+    const void* dh;
+    const float* weight;
+    const int64_t* comp;
+    const int64_t* ids;
+    const int64_t* allowed;
+    float* grad;
+    float* gxi;
+    int64_t rows;
+    int D, V, n_strands, A, centre;
+    int dtype;
+};
+typedef struct cad_embed_attrib_args cad_embed_attrib_args;
+int cad_embed_attrib(const cad_embed_attrib_args* a, void* stream);
+int cad_embed_attrib_supported(int D, int V, int dtype);
+
 /* Unmask head: one round of iterative unmasking (masked infilling with a bi-directional or RCPS model) straight from the final hidden
  * state, in one launch; neither logits nor log-probabilities are written per vocabulary entry.  Row i = b L + l of hidden is OPEN iff
  * ids_in[i] == mask_id.
