@@ -98,8 +98,12 @@ def causal_conv1d(x, w, bias, split, rev_lo, rev_hi):
         raise NotImplementedError("sequence-parallel conv supports d_conv <= 4")
     if x.shape[-1] < HALO:
         raise ValueError("sequence-parallel segments must hold at least 3 positions")
-    ext = _HaloExchange.apply(x, _GROUP)
-    return ops.causal_conv1d(ext, w, bias, split, rev_lo, rev_hi)[..., HALO:-HALO].contiguous()
+    # 16-bit activations run the segment's conv and the halo exchange in fp32 on the same stored values and round once at the end: dx at
+    # the HALO positions on either side of a cut is a sum of two ranks' parts, and parts stored in bf16 and added in bf16 carried three
+    # roundings -- two of them relative to parts that may cancel -- where the single-process kernel rounds its fp32 sum once
+    ext = _HaloExchange.apply(x if x.dtype == torch.float32 else x.float(), _GROUP)
+    out = ops.causal_conv1d(ext, w, bias, split, rev_lo, rev_hi)[..., HALO:-HALO]
+    return out.to(x.dtype).contiguous()
 
 
 # ---- selective scan with state hand-off --------------------------------------------------------------------------------
@@ -179,20 +183,22 @@ class _ScanSeqPar(torch.autograd.Function):
         npart = lib.cad_scan_bwd_partials(sets[0][0].shape[0])
         douts = [d.contiguous() for d in douts]
 
-        def launch(dhTs):
-            # gate_fix=None is a known gap: no worklist, and no cad_scan_bwd_gate_fix behind the scan (lost gates keep the plain gradient)
-            args, res, stream = ops.scan_bwd_sets(lib, sets, z, douts, split, dirs, npart=npart, dhTs=dhTs, dh0=True, gate_fix=None)
+        def launch(dhTs, gate_fix):
+            args, res, stream = ops.scan_bwd_sets(lib, sets, z, douts, split, dirs, npart=npart, dhTs=dhTs, dh0=True, gate_fix=gate_fix)
             L.check(lib.cad_scan_bwd_multi(args, nsets, stream), "cad_scan_bwd_multi")
+            if gate_fix is not None and z is not None:  # exact gate gradient at lost gates, as ops._ScanMulti.backward
+                L.check(lib.cad_scan_bwd_gate_fix(args, nsets, stream), "cad_scan_bwd_gate_fix")
             return res, stream
 
-        # pass 1: state-gradient map of the segment, zero gradient entering from the far side (known gap: a full pass, not carry_only)
-        first, _ = launch(None)
+        # pass 1: state-gradient map of the segment, zero gradient entering from the far side (known gap: a full pass, not carry_only);
+        # only its dh0 is used, so it keeps no worklist of lost gates
+        first, _ = launch(None, None)
         dhTs = []
         for i in range(nsets):
             G_all = _all_gather(first[i][0]["dh0"], group)
             P_all = list(flat[10 * i + 9].unbind(0))
             dhTs.append(_compose(P_all, G_all, rank, split, dirs[i][0], dirs[i][1], towards_end=True).contiguous())
-        res, stream = launch(dhTs)
+        res, stream = launch(dhTs, ops.gate_fix_buffers)
         grads, dz = ops.scan_bwd_grads(res, pdt, stream, dz_in_place=False)
         return (None, dz, None, None, *[g for set_grads in grads for g in set_grads])
 
